@@ -17,7 +17,18 @@ How N GPUs are driven (`--gpus N`):
 Either way: barrier + device sync on both sides of the K timed steps, the
 max over ranks, `value` = grid points of all GPUs / that time.
 
-Also reported (same JSON line):
+A plain run does only what the headline needs: it makes the batch, ramps and
+warms up, times the K steps of K1, writes its outputs if asked (below) and
+prints the line (the headline's fields and its roofline record, from the timed
+steps' own events). Everything else is behind `--full`.
+
+`--dump-outputs DIR`: after the timed steps, the dense X/Y/Z planes K1 wrote in
+its last timed step, as a caller reads them (Batch.read_dense), for a fixed,
+seeded sample of frames (at most 64 MB in all): DIR/k1_xyz_frame<global id>.npy,
+float32 (3, Hg, pitch). The frames are generated from their global ids, so the
+same arguments give the same inputs and the same files from run to run.
+
+With `--full`, also reported (same JSON line; each part has a --no-* switch):
   pipeline      configs[3]/[4]: plane threshold + hue histogram + ordered
                 compaction + int32 back-projection over the same batch; for
                 N > 1 every step starts with the RCCL broadcast of the plane
@@ -35,7 +46,7 @@ Also reported (same JSON line):
                 host core: stereovision.py:84-113 for frame 0 at step 2, per
                 stage; rank 0 at N = 1 only.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
        torchrun --nproc-per-node N bench.py --gpus N ...
 """
 import argparse
@@ -77,6 +88,12 @@ def parse(argv=None):
     ap.add_argument("--ramp-ms", type=float, default=300.0,
                     help="untimed launches before the warmup steps of K1 and of the pipeline (a third of it before the "
                          "§8f stage timings), to let clocks settle")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the pipeline, the per-frame parity checks, the "
+                         "1-frame latency, the SURVEY §8f extras and the CPU baseline (each has a --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the K1 planes of the last timed step for a fixed sample of frames (at most 64 MB) "
+                         "as DIR/k1_xyz_frame<global id>.npy")
     ap.add_argument("--no-pipeline", action="store_true")
     ap.add_argument("--no-latency", action="store_true", help="skip the 1-frame latency probe")
     ap.add_argument("--no-cpu", action="store_true")
@@ -89,7 +106,10 @@ def parse(argv=None):
     ap.add_argument("--traffic", default=os.path.join(REPO, "profiles", "traffic.json"))
     ap.add_argument("--traffic-pipeline", default=os.path.join(REPO, "profiles", "traffic_pipeline.json"))
     ap.add_argument("--traffic-planes", default=os.path.join(REPO, "profiles", "traffic_planes.json"))
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if not args.full:   # a plain run: the headline alone
+        args.no_pipeline = args.no_latency = args.no_cpu = args.no_extras = args.no_parity = True
+    return args
 
 
 def plan(gpus, environ, driver="auto"):
@@ -134,6 +154,33 @@ def aggregate(ctrl, n_gpus, points_local, steps, dt_local):
     dt = float(ctrl.max([dt_local])[0])
     points = float(ctrl.sum([points_local])[0]) * steps
     return {"n_gpus": n_gpus, "value": points / dt / 1e6, "ms_per_step": dt / steps * 1e3, "points": points}
+
+
+DUMP_LIMIT = 64 * 1000 * 1000   # bytes --dump-outputs writes at most
+DUMP_SEED = 20240607
+
+
+def dump_frames(total, frame_bytes):
+    """The global frame ids --dump-outputs writes: every frame while they fit DUMP_LIMIT, else a fixed draw
+    (DUMP_SEED) of as many as fit, the same for every run and every split of the frames over GPUs."""
+    n = max(1, min(total, DUMP_LIMIT // frame_bytes))
+    if n >= total:
+        return list(range(total))
+    return sorted(int(f) for f in np.random.default_rng(DUMP_SEED).choice(total, n, replace=False))
+
+
+def dump_outputs(path, batches, shards, total):
+    """K1's dense planes as a caller reads them (Batch.read_dense: X, Y, Z, fp32 Hg x pitch) for the sampled
+    frames this process holds, one (3, Hg, pitch) file a frame; returns the ids written."""
+    os.makedirs(path, exist_ok=True)
+    ids = dump_frames(total, 3 * 4 * batches[0].Hg * batches[0].pitch)
+    done = []
+    for b, (_, first, count) in zip(batches, shards):
+        for f in ids:
+            if first <= f < first + count:
+                np.save(os.path.join(path, f"k1_xyz_frame{f:07d}.npy"), np.stack(b.read_dense(f - first)))
+                done.append(f)
+    return done
 
 
 def carmask():
@@ -724,6 +771,9 @@ def main(argv=None):
     k_avg_s = float(ctrl.max([max(ms / max(n, 1) for ms, n in (b.timing("project") for b in batches)) / 1e3])[0])
     bytes_launch = K1_BYTES_PER_POINT * ng * batches[0].frames
     achieved = bytes_launch / k_avg_s / 1e9
+    if args.dump_outputs:   # the last timed step's planes, before anything else runs on the batch
+        dump_outputs(args.dump_outputs, batches, shards,
+                     args.global_frames if strong else args.frames * pl["n_gpus"])
 
     k1_name = batches[0].kernel_name("project")
     traffic, traffic_why = profile_traffic(args.traffic, batches[0].frames, args.step, k1_name, "k1")

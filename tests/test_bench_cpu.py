@@ -111,6 +111,30 @@ def test_strong_scaling_shards(n):
         bench.shards_of(bench.plan(8, {}), 4096, 4)
 
 
+def test_plain_run_is_the_headline_alone():
+    """Without --full every leg beside the headline is off; --full turns them on, less the --no-* given."""
+    legs = ("no_pipeline", "no_latency", "no_cpu", "no_extras", "no_parity")
+    a = bench.parse(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert not a.full and a.dump_outputs is None and a.steps == 5 and a.warmup == 2
+    assert all(getattr(a, k) for k in legs)
+    a = bench.parse(["--full"])
+    assert a.full and not any(getattr(a, k) for k in legs)
+    a = bench.parse(["--full", "--no-cpu", "--dump-outputs", "d"])
+    assert a.no_cpu and not a.no_pipeline and a.dump_outputs == "d"
+
+
+def test_dump_frames_is_a_fixed_sample_within_the_limit():
+    """--dump-outputs' frames: all of a small batch; of the 4096-frame batch as many 1024x544 step-1 frames as fit
+    64 MB, distinct, in range, and the same draw every time."""
+    fb = 3 * 4 * 543 * 1024
+    assert bench.dump_frames(4, fb) == [0, 1, 2, 3]
+    ids = bench.dump_frames(4096, fb)
+    assert ids == bench.dump_frames(4096, fb) == sorted(set(ids))
+    assert len(ids) == bench.DUMP_LIMIT // fb == 9 and 0 <= ids[0] and ids[-1] < 4096
+    assert len(ids) * fb <= bench.DUMP_LIMIT == 64 * 1000 * 1000
+    assert len(bench.dump_frames(4096, 2 * bench.DUMP_LIMIT)) == 1
+
+
 def _traffic_file(tmp_path, **kw):
     import json
     tj = {"frames": 4096, "step": 1, "pipeline_kernels": {

@@ -11,7 +11,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ARGS = ["--gpus", "1", "--frames", "512", "--steps", "2", "--warmup", "1", "--ramp-ms", "20",
-        "--no-extras", "--no-cpu", "--no-latency"]
+        "--full", "--no-extras", "--no-cpu", "--no-latency"]
 
 
 def _check(out):
@@ -63,6 +63,45 @@ def test_bench_ranks_driver(monkeypatch):
     assert "torchrun" in out["config"]["parallelism"]
     assert out["pipeline"]["plane_broadcast"].startswith("RCCL ncclBroadcast")
     assert len(calls) >= 3
+
+
+def test_bench_plain_run_and_dump_outputs(monkeypatch, tmp_path):
+    """A plain run (no --full) times the headline alone: no pipeline, parity, latency, extras or CPU records in its
+    line. --dump-outputs writes the last timed step's K1 planes for the fixed frame sample (16 frames of 6.7 MB do
+    not fit the 64 MB limit, so the seeded draw is taken): the same files from two runs, each frame's planes the
+    oracle's projection of that frame within fp32 rounding."""
+    import os
+
+    import numpy as np
+
+    import bench
+    import oracle
+    for v in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        monkeypatch.delenv(v, raising=False)
+    args = ["--gpus", "1", "--frames", "16", "--steps", "3", "--warmup", "1", "--ramp-ms", "20"]
+    outs = [bench.main(args + ["--dump-outputs", str(tmp_path / d)]) for d in ("a", "b")]
+    for out in outs:
+        assert out["steps"] == 3 and out["value"] > 0 and out["ms_per_step"] > 0
+        for k in ("metric", "unit", "higher_is_better", "dtype", "roofline"):
+            assert k in out, k
+        for k in ("pipeline", "parity", "latency_1frame_us", "extras", "cpu_baseline"):
+            assert k not in out, k
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b"))
+    ids = bench.dump_frames(16, 3 * 4 * 543 * 1024)
+    assert names == [f"k1_xyz_frame{f:07d}.npy" for f in ids] and 1 < len(ids) < 16
+    total = 0
+    for f, name in zip(ids, names):
+        a = np.load(tmp_path / "a" / name)
+        assert a.dtype == np.float32 and a.shape == (3, 543, 1024)
+        assert np.array_equal(a.view(np.uint32), np.load(tmp_path / "b" / name).view(np.uint32))
+        total += a.nbytes
+        disp, _ = oracle.synth_frame(f)
+        ref = oracle.project_dense(disp, 1)
+        assert np.array_equal(a[2] == 0, ref[2] == 0)
+        for got, want in zip(a, ref):
+            np.testing.assert_allclose(got, want, rtol=1e-5, atol=0)
+    assert total <= bench.DUMP_LIMIT
 
 
 def test_bench_strong_scaling_flag(monkeypatch):

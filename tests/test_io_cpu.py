@@ -3,7 +3,7 @@
 A minimal encoder below writes PNGs with every scanline filter (None, Sub, Up, Average, Paeth) and every 8-bit
 colour type; reading them back must give the samples exactly, with OpenCV's channel handling (BGR order, alpha
 stripped, grey replicated, palette expanded) and libpng's rgb_to_gray for IMREAD_GRAYSCALE. The reference's own
-masks are decoded when the reference checkout is present (this container only; never on the GPU box).
+masks (the five PNG files of its masks/ folder, stored as fixtures in tests/golden/masks/) are decoded too.
 """
 import os
 import struct
@@ -14,7 +14,7 @@ import pytest
 
 from svx import io as sio
 
-REF_MASKS = "/root/reference/masks"
+REF_MASKS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "masks")
 
 
 def _filter_row(ft, row, prev, bpp):
@@ -241,7 +241,6 @@ def test_load_images_pairs_in_bgr(tmp_path):
     np.testing.assert_array_equal(r, right[..., ::-1])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MASKS), reason="the reference checkout (this container only)")
 def test_reference_masks_decode():
     """functions.py:29-35 on the reference's own masks: 1024 x 544 RGBA, black and white; plane_sample.png is
     absent (None, as the reference loads it); carmask covers 22.97 % of the pixels (measured)."""

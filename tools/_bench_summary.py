@@ -1,4 +1,4 @@
-"""Key numbers of a bench.py log's JSON line (the last one): python tools/_bench_summary.py LOG"""
+"""Key numbers of a `bench.py --full` log's JSON line (the last one): python tools/_bench_summary.py LOG"""
 import json
 import sys
 

@@ -6,7 +6,7 @@ mkdir -p gpurun_out
 R=$1; A=$2; B=$3; shift 3
 for r in $(seq 1 "$R"); do
   for lib in "$A" "$B"; do
-    SVX_LIB="$PWD/$lib" timeout -k 10 120 python bench.py --no-extras --no-latency --no-cpu --no-parity "$@" \
+    SVX_LIB="$PWD/$lib" timeout -k 10 120 python bench.py --full --no-extras --no-latency --no-cpu --no-parity "$@" \
       > gpurun_out/ab_bench_run.log 2>&1 || { echo "FAIL rc=$? $lib"; tail -5 gpurun_out/ab_bench_run.log; exit 1; }
     python3 -c "
 import json,sys

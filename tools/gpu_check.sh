@@ -16,11 +16,11 @@ rc=$?; echo "pytest rc=$rc"; tail -25 "$OUT/pytest_gpu.log"; stop_if_fatal $rc p
 export TMPDIR=/tmp
 if [ "${SKIP_PROF:-0}" != 1 ]; then
   timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-    python3 bench.py ${BENCH_ARGS:---steps 10 --warmup 2 --cpu-seconds 10} > "$OUT/bench.log" 2>&1
+    python3 bench.py --full ${BENCH_ARGS:---steps 10 --warmup 2 --cpu-seconds 10} > "$OUT/bench.log" 2>&1
   rc=$?; echo "bench (rocprof) rc=$rc"; tail -2 "$OUT/bench.log"; stop_if_fatal $rc bench
   find "$OUT/prof" -name "*stats*" | head
 else
-  timeout -k 10 600 python bench.py ${BENCH_ARGS:---steps 10 --warmup 2 --cpu-seconds 10} > "$OUT/bench.log" 2>&1
+  timeout -k 10 600 python bench.py --full ${BENCH_ARGS:---steps 10 --warmup 2 --cpu-seconds 10} > "$OUT/bench.log" 2>&1
   rc=$?; echo "bench rc=$rc"; tail -2 "$OUT/bench.log"; stop_if_fatal $rc bench
 fi
 if [ -n "${SWEEP:-}" ]; then

@@ -1,5 +1,5 @@
 #!/bin/bash
-# One GPU-box evidence session: the GPU suite, smoke, the default bench under rocprofv3 --kernel-trace --stats
+# One evidence session on a GPU: the GPU suite, smoke, bench.py --full under rocprofv3 --kernel-trace --stats
 # (JSON line + per-kernel stats from the same process), then PMC HBM traffic of K1 / the pipeline / the
 # per-frame-plane pipeline at the bench workload (profiles bench.py matches by kernel instance and sources).
 # Every GPU step has its own time limit; a fault, abort or timeout ends the script (no retries).
@@ -16,7 +16,7 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
 fi
 if [ "${SKIP_BENCH:-0}" != 1 ]; then
   timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-    python3 -u bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+    python3 -u bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
   rc=$?; echo "bench rc=$rc"; tail -c 600 "$OUT/bench.json"; ok $rc bench
 fi
 if [ "${SKIP_PMC:-0}" != 1 ]; then

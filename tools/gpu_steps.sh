@@ -1,6 +1,6 @@
 #!/bin/bash
 # Named GPU-box steps for one gpurun call: tools/gpu_steps.sh TAG step [step ...]
-#   tests    the GPU suite + smoke          bench   the default bench under rocprofv3 --kernel-trace --stats
+#   tests    the GPU suite + smoke          bench   bench.py --full under rocprofv3 --kernel-trace --stats
 #   ablate   tools/gpu_ransac_ablate_check  pmc     PMC HBM traffic of K1 / pipeline / per-frame planes
 #   ab_fill  fill_prev one-wave vs loader/writer split (SVX_FILL_SPLIT, diagnostic build, child processes)
 #   ab_pipe  the resident pipeline, SVX_ABLATE / env A/B (ARGS_AB_PIPE)
@@ -20,7 +20,7 @@ for step in "$@"; do
     rc=$?; echo "smoke rc=$rc"; tail -1 "$OUT/smoke.log"; ok $rc smoke ;;
   bench)
     timeout -k 10 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-      python3 -u bench.py ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
+      python3 -u bench.py --full ${BENCH_ARGS:-} > "$OUT/bench.json" 2> "$OUT/bench.err"
     rc=$?; echo "bench rc=$rc"; tail -c 400 "$OUT/bench.json"; ok $rc bench ;;
   ablate)
     TAG=$TAG bash tools/gpu_ransac_ablate_check.sh; ok $? ablate ;;
