@@ -112,6 +112,26 @@ int sv_road_raster(const int32_t* pts, int64_t n, int H, int W, uint8_t* out_img
 /* The pixel walk at the end of functions.py:355-366 (sanitiseRoadImage):
  * out = [j, i] (int32) of every non-zero pixel, raster order. W <= 4096. */
 int sv_nonzero_points(const uint8_t* img, int H, int W, int32_t* out, int64_t cap, int64_t* out_n);
+/* Replaces functions.py:346-366 sanitiseRoadImage(img, size): the road image's clean-up and its pixel walk.
+ * img: H x W u8, non-zero pixels are "set"; mask: H x W u8 (road_threshold_mask, functions.py:31), NULL = all
+ * ones. out_img (nullable): H x W u8 holding only 0 or 255. The steps, exactly:
+ *   1. close by a 9 x 9 rectangle (cv2.morphologyEx MORPH_CLOSE, :351): dilate with radius 4, then erode with
+ *      radius 4, anchor at the centre, OpenCV's default morphology borders — for the dilation pixels outside
+ *      the image count as clear, for the erosion they count as set, so the border never clears a pixel;
+ *   2. erode by 9 x 9 twice (:353), which with that border is one erosion by 17 x 17 (radius 8);
+ *   3. AND with mask != 0 (cv2.bitwise_and(img, img, mask=m), :355: a mask pixel of 128 keeps the pixel);
+ *   4. close by 9 x 9 again (:356);
+ *   5. ParticleCleansing (:358, :378-384) is the identity on step 4's result (it fills external contours of
+ *      area < 70; a hole that survives a 9 x 9 close holds a full 9 x 9 block of zeros, so its contour's area
+ *      is above 81: DESIGN.md) and has no kernel;
+ *   6. the walk (:359-365): out_pts (nullable, cap x 2 int32) = [j, i] of every non-zero pixel in raster order,
+ *      *out_n (nullable) their number; SV_E_CAP when out_pts holds fewer (as sv_nonzero_points).
+ * All four operations are rectangular, done separably on a bitmap (rows, then columns); the chain's vertical
+ * reach is 4 + 4 + 8 + 4 + 4 = 24 rows. The steps restate cv2 calls (cv2 is absent here): their parity with the
+ * reference's OpenCV is unpinned, like fillDisparity / maskDisparity. 2 <= W <= 4096, H * W < 2^28. Host,
+ * synchronous. */
+int sv_sanitise_road(const uint8_t* img, const uint8_t* mask, int H, int W, uint8_t* out_img, int32_t* out_pts,
+                     int64_t cap, int64_t* out_n);
 
 /* ---- the stages a2-a6 one by one (the stage drop-ins) ---------------------- */
 
@@ -290,6 +310,20 @@ int sv_batch_road_map(sv_batch* b, int enable);
  * keep the points path. */
 int sv_batch_road_bits(sv_batch* b, int enable);
 int sv_batch_read_road_map(sv_batch* b, int frame, uint8_t* out);
+/* sanitiseRoadImage's clean-up (sv_sanitise_road's steps 1-6) of every frame's road image, on the device.
+ * sv_batch_road_mask: the H x W road_threshold_mask of step 3 (NULL clears it to all ones).
+ * sv_batch_road_clean needs a current road pass (sv_batch_road_raster after the last pipeline call, else
+ * SV_E_STATE); it reads the pipeline's road bitmap when that is fresh (sv_batch_road_bits) and packs the road
+ * images otherwise, and writes the cleaned images and their walks into buffers of its own:
+ * sv_batch_read_road keeps returning the raw image and walk, sv_batch_read_road_clean (same contract) the
+ * cleaned ones. 1024-wide frames of up to 1024 rows get image and walk from the bitmap road pass, others from
+ * an unpack kernel and the non-zero walk. */
+int sv_batch_road_mask(sv_batch* b, const uint8_t* mask);
+int sv_batch_road_clean(sv_batch* b, int sync);
+int sv_batch_read_road_clean(sv_batch* b, int frame, uint8_t* img, int32_t* nzpts, int64_t cap, int64_t* n);
+/* ms of the last sv_batch_road_clean from HIP events on the batch stream: *kernel_ms the clean-up kernel alone,
+ * *total_ms the whole call's device work (pack, clean-up, image + walk). Synchronises the batch stream. */
+int sv_batch_road_clean_ms(sv_batch* b, float* kernel_ms, float* total_ms);
 
 /* Batched RANSAC (stereovision.py:84-94 for every frame):
  * maskpoints = the fp64 step-2 projection of the batch's disparity under the
@@ -409,13 +443,19 @@ typedef struct {
     uint64_t seed_base;  /* frame g draws what CPython draws after random.seed(seed_base + g)           */
     double point_thr;    /* computePlanarThreshold threshold (0.05)                                    */
     int hist_thr;        /* filterPointsByHistogram threshold (10)                                     */
-    int road;            /* 0 none, 1 road raster + walk, 2 + imageRoadMap                             */
+    int road;            /* 0 none, 1 road raster + walk, 2 + imageRoadMap, 3 road raster + walk + the
+                            clean-up (sv_batch_road_clean; its mask: sv_loop_road_mask)                 */
 } sv_loop_params;
 typedef struct sv_loop sv_loop;
 /* carmask: the grey H x W mask of maskDisparity (functions.py:35, :169-172), NULL for none. */
 int sv_loop_create(int device, const sv_loop_params* prm, const sv_camera* cam, const uint8_t* carmask,
                    sv_loop** out);
 int sv_loop_destroy(sv_loop* L);
+/* road = 3: the road stage of every batch also runs sanitiseRoadImage's clean-up (it counts inside the
+ * timeline's "road" stage); the cleaned images and walks are on the batch sv_loop_batch returns
+ * (sv_batch_read_road_clean). mask: the H x W road_threshold_mask for every slot, NULL = all ones (the default);
+ * it applies to the batches whose road stage is enqueued after the call. */
+int sv_loop_road_mask(sv_loop* L, const uint8_t* mask);
 /* The batch the next sv_loop_submit runs (waits on the host until its slot's previous batch is done): with
  * source 0 the caller uploads its frames (or runs sv_batch_sgbm on it) before submitting. */
 int sv_loop_acquire(sv_loop* L, sv_batch** out);

@@ -16,6 +16,7 @@
 
 #include "../../include/svx.h"
 #include "svx_launch.h"
+#include "svx_morph.h"
 #include "svx_sgbm.h"
 
 using namespace svx;
@@ -148,6 +149,7 @@ struct Device {
     std::mutex mu;
     // drop-in scratch
     DevBuf disp, bgr, xyz, rgb, ctrl, xy, aux, aux2;
+    DevBuf mbits;                     // sv_sanitise_road: the image, the cleaned image and the mask as bitmaps
     DevBuf sg_l, sg_r, sg_out, sg_filt, sg_hist;   // host-frame SGBM / grey drop-ins
     SgbmBufs sg;
     Tables tables;
@@ -287,6 +289,15 @@ struct sv_batch {
     bool rbits_fresh = false;   // rbits holds the bitmap of the current pipeline points
     DevBuf rbits, roff;         // the bitmap (frames x H x 32 words); the road pass's per-row walk offsets
     bool want_rmap = false, rmap_fresh = false;
+    // sanitiseRoadImage's clean-up (sv_batch_road_clean): the mask as a bitmap (behind its staged bytes), the packed
+    // road images (when the pipeline wrote no bitmap), the cleaned bitmaps, images, walks (frames x ccap packed
+    // entries: a cleaned image can hold more pixels than the pipeline has points), counts and row offsets
+    DevBuf rmask, cpack, cbits, cimg, cnz, cnzcount, croff;
+    bool have_rmask = false;
+    bool road_fresh = false;    // road holds the images of the current pipeline points (sv_batch_road_raster ran)
+    bool clean_fresh = false;   // cimg / cnz hold the clean-up of the current road images
+    size_t ccap = 0;            // walk entries per frame of cnz: H x Wu rounded up to 64
+    hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};   // start, clean-up kernel's start / end, end
     DevBuf mpts, rres;          // one frame's maskpoints as fp64 (read-back scratch); counts + batched RANSAC results
     DevBuf prev0buf, rdbuf;     // the host prev0 of sv_batch_prepass; sv_batch_read_disp's masked frame (batch-owned:
                                 // the device-wide drop-in scratch is used on other streams)
@@ -630,12 +641,15 @@ int sv_batch_destroy(sv_batch* b) {
     for (DevBuf* x : {&b->disp, &b->bgr, &b->X, &b->Y, &b->Z, &b->oxb, &b->oyb, &b->ozb, &b->xyz, &b->ppxy, &b->ctrl, &b->masks,
                       &b->carmask, &b->road, &b->rmap, &b->nz, &b->nzcount, &b->mpts, &b->mpk, &b->rres, &b->rtab, &b->rtrace, &b->fplanes, &b->dplane, &b->abc,
                       &b->pairL, &b->pairR, &b->rsidx, &b->rtri, &b->bgrL, &b->bgrR,
-                      &b->glut, &b->ghist, &b->sgflags, &b->prev0buf, &b->rdbuf, &b->rbits, &b->roff, &b->raw})
+                      &b->glut, &b->ghist, &b->sgflags, &b->prev0buf, &b->rdbuf, &b->rbits, &b->roff, &b->raw, &b->rmask, &b->cpack,
+                      &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff})
         if (x->p) (void)hipFree(x->p);
     if (b->hcnt) (void)hipHostFree(b->hcnt);
     if (b->cnt_ev) (void)hipEventDestroy(b->cnt_ev);
     b->sg.release();
     for (auto& ev : b->ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : b->cev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->pool) (void)hipEventDestroy(ev);
     for (auto& ev : b->sync_ev) (void)hipEventDestroy(ev);
@@ -931,6 +945,7 @@ static int batch_pipeline_impl(sv_batch* b, const sv_camera* cam, const sv_plane
         bf.plane_stride = 0;
     }
     b->rbits_fresh = false;
+    b->road_fresh = b->clean_fresh = false;   // the road images no longer belong to the points
     if (mode >= 2 && b->road_bits && resident_road_bits_supported(p)) {   // the road bitmap too (sv_batch_road_bits)
         HIP_TRY(b->rbits.ensure(sizeof(uint32_t) * 32 * (size_t)b->H * b->frames));
         bf.rbits = b->rbits.as<uint32_t>();
@@ -1439,6 +1454,8 @@ int sv_batch_road_raster(sv_batch* b, int sync) {
     const char* v = svx_knob("SVX_ROAD_FUSED");
     b->nz_fresh = !(v && v[0] == '0');
     b->rmap_fresh = false;
+    b->road_fresh = true;
+    b->clean_fresh = false;
     if (b->nz_fresh) {
         uint8_t* paint = nullptr;
         if (b->want_rmap) {   // imageRoadMap in the same pass (stereovision.py:131-133)
@@ -1527,6 +1544,180 @@ int sv_batch_read_road(sv_batch* b, int frame, uint8_t* img, int32_t* nzpts, int
                 nzpts[2 * i] = (int32_t)(pk[(size_t)i] & 0xFFFFu);
                 nzpts[2 * i + 1] = (int32_t)(pk[(size_t)i] >> 16);
             }
+        }
+    }
+    return SV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// sanitiseRoadImage's clean-up (functions.py:346-366): kernels/morph.hip, then the image and the walk
+// ---------------------------------------------------------------------------
+
+// 1024-wide frames of up to 1024 rows: the bitmap road pass (launch_road_bits) makes image and walk from the
+// cleaned bitmap; other shapes: unpack, then the non-zero walk
+static bool clean_by_road_bits(int H, int Wu) { return Wu == 1024 && H <= 1024; }
+
+// packed walk entries (x | y << 16, walk_pk) widened to the reference's [x, y] int32 pairs
+static void widen_walk(const std::vector<uint32_t>& pk, int32_t* out) {
+    for (size_t i = 0; i < pk.size(); ++i) {
+        out[2 * i] = (int32_t)(pk[i] & 0xFFFFu);
+        out[2 * i + 1] = (int32_t)(pk[i] >> 16);
+    }
+}
+
+int sv_sanitise_road(const uint8_t* img, const uint8_t* mask, int H, int W, uint8_t* out_img, int32_t* out_pts,
+                     int64_t cap, int64_t* out_n) {
+    if (!img || H < 0 || W < 2 || W > 4096 || (int64_t)H * W >= (1ll << 28) || (out_pts && cap < 0))
+        return fail(SV_E_ARG, "sv_sanitise_road: bad arguments (2 <= W <= 4096, H*W < 2^28)");
+    if (out_n) *out_n = 0;
+    if (H == 0) return SV_OK;
+    int dev;
+    if (int rc = current_device(&dev)) return rc;
+    Device* d;
+    if (int rc = dev_get(dev, &d)) return rc;
+    std::lock_guard<std::mutex> lk(d->mu);
+    hipStream_t s = d->stream;
+    const int pitch = (W + 7) / 8 * 8, WW = (W + 31) / 32;
+    const size_t px = (size_t)H * pitch, words = (size_t)H * WW;
+    // bitmaps: the image | the cleaned image | the mask | (bitmap road pass) the rows' walk offsets
+    HIP_TRY(d->mbits.ensure(sizeof(uint32_t) * (3 * words + (size_t)H)));
+    uint32_t* bin = d->mbits.as<uint32_t>();
+    uint32_t* bout = bin + words;
+    uint32_t* bmask = bout + words;
+    int32_t* roff = reinterpret_cast<int32_t*>(bmask + words);
+    if (int rc = upload_u8(d->aux, img, H, W, pitch, s)) return rc;
+    HIP_TRY(launch_morph_pack(d->aux.as<uint8_t>(), (int64_t)px, pitch, W, H, 1, bin, s));
+    if (mask) {
+        if (int rc = upload_u8(d->aux2, mask, H, W, pitch, s)) return rc;
+        HIP_TRY(launch_morph_pack(d->aux2.as<uint8_t>(), (int64_t)px, pitch, W, H, 1, bmask, s));
+    }
+    HIP_TRY(launch_morph_clean(bin, mask ? bmask : nullptr, bout, 1, H, W, s));
+    // the image (into aux: the pack above has read it, in stream order) and the walk
+    const bool bits_pass = clean_by_road_bits(H, W);
+    HIP_TRY(d->xy.ensure(sizeof(int32_t) * 2 * px + 64));
+    int64_t* cnt = reinterpret_cast<int64_t*>(d->xy.as<char>() + sizeof(int32_t) * 2 * px);
+    if (bits_pass) {   // packed walk entries (x | y << 16)
+        HIP_TRY(launch_road_bits(bout, 1, H, W, roff, (int64_t)px, d->aux.as<uint8_t>(), d->xy.as<int32_t>(), cnt,
+                                 nullptr, nullptr, s));
+    } else {           // [x, y] int32 pairs
+        HIP_TRY(launch_morph_unpack(bout, 1, H, W, pitch, d->aux.as<uint8_t>(), s));
+        HIP_TRY(launch_nonzero(d->aux.as<uint8_t>(), 1, (int64_t)px, pitch, d->xy.as<int32_t>(), (int64_t)px, cnt,
+                               false, s));
+    }
+    int64_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, cnt, sizeof n, hipMemcpyDeviceToHost, s));
+    if (out_img) HIP_TRY(hipMemcpy2DAsync(out_img, W, d->aux.p, pitch, W, H, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out_n) *out_n = n;
+    if (!out_pts || n == 0) return SV_OK;
+    if (n > cap) return fail(SV_E_CAP, "capacity %lld < %lld non-zero pixels", (long long)cap, (long long)n);
+    if (bits_pass) {
+        std::vector<uint32_t> pk((size_t)n);
+        HIP_TRY(hipMemcpyAsync(pk.data(), d->xy.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        widen_walk(pk, out_pts);
+    } else {
+        HIP_TRY(hipMemcpyAsync(out_pts, d->xy.p, sizeof(int32_t) * 2 * n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return SV_OK;
+}
+
+int sv_batch_road_mask(sv_batch* b, const uint8_t* mask) {
+    if (!b) return fail(SV_E_ARG, "null batch");
+    HIP_TRY(hipSetDevice(b->device));
+    b->clean_fresh = false;
+    if (!mask) {
+        b->have_rmask = false;
+        return SV_OK;
+    }
+    if (b->Wu > 4096) return fail(SV_E_ARG, "the road clean-up takes frames up to 4096 wide");
+    const size_t px = (size_t)b->H * b->W, words = (size_t)b->H * ((b->Wu + 31) / 32);
+    HIP_TRY(b->rmask.ensure(px + sizeof(uint32_t) * words));   // the staged bytes, then the bitmap (px % 8 == 0)
+    uint8_t* grey = b->rmask.as<uint8_t>();
+    HIP_TRY(hipMemsetAsync(grey, 0, px, b->stream));
+    HIP_TRY(hipMemcpy2DAsync(grey, b->W, mask, b->Wu, b->Wu, b->H, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(launch_morph_pack(grey, (int64_t)px, b->W, b->Wu, b->H, 1, reinterpret_cast<uint32_t*>(grey + px),
+                              b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->have_rmask = true;
+    return SV_OK;
+}
+
+int sv_batch_road_clean(sv_batch* b, int sync) {
+    if (!b) return fail(SV_E_ARG, "null batch");
+    if (!b->road.p || !b->road_fresh)
+        return fail(SV_E_STATE, "no current road pass (sv_batch_road_raster after the pipeline first)");
+    if (b->Wu < 2 || b->Wu > 4096) return fail(SV_E_ARG, "the road clean-up takes frames 2..4096 wide");
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    const int H = b->H, Wu = b->Wu, WW = (Wu + 31) / 32;
+    const size_t px = (size_t)H * b->W, words = (size_t)H * WW;
+    for (hipEvent_t& e : b->cev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    b->clean_fresh = false;
+    b->ccap = ((size_t)H * Wu + 63) / 64 * 64;
+    HIP_TRY(b->cbits.ensure(sizeof(uint32_t) * words * b->frames));
+    HIP_TRY(b->cimg.ensure(px * b->frames));
+    HIP_TRY(b->cnz.ensure(sizeof(uint32_t) * b->ccap * b->frames));   // packed entries x | y << 16 (walk_pk)
+    HIP_TRY(b->cnzcount.ensure(sizeof(int64_t) * b->frames));
+    HIP_TRY(hipEventRecord(b->cev[0], s));
+    const uint32_t* src;
+    if (b->rbits_fresh && Wu == 1024) {   // the pipeline's own bitmap of the road pixels (32 words a row)
+        src = b->rbits.as<uint32_t>();
+    } else {
+        HIP_TRY(b->cpack.ensure(sizeof(uint32_t) * words * b->frames));
+        HIP_TRY(launch_morph_pack(b->road.as<uint8_t>(), (int64_t)px, b->W, Wu, H, b->frames, b->cpack.as<uint32_t>(), s));
+        src = b->cpack.as<uint32_t>();
+    }
+    const uint32_t* mk = b->have_rmask ? reinterpret_cast<const uint32_t*>(b->rmask.as<uint8_t>() + px) : nullptr;
+    HIP_TRY(hipEventRecord(b->cev[1], s));
+    HIP_TRY(launch_morph_clean(src, mk, b->cbits.as<uint32_t>(), b->frames, H, Wu, s));
+    HIP_TRY(hipEventRecord(b->cev[2], s));
+    if (clean_by_road_bits(H, Wu)) {
+        HIP_TRY(b->croff.ensure(sizeof(int32_t) * (size_t)H * b->frames));
+        HIP_TRY(launch_road_bits(b->cbits.as<uint32_t>(), b->frames, H, b->W, b->croff.as<int32_t>(), (int64_t)b->ccap,
+                                 b->cimg.as<uint8_t>(), b->cnz.as<int32_t>(), b->cnzcount.as<int64_t>(), nullptr,
+                                 nullptr, s));
+    } else {
+        HIP_TRY(launch_morph_unpack(b->cbits.as<uint32_t>(), b->frames, H, Wu, b->W, b->cimg.as<uint8_t>(), s));
+        HIP_TRY(launch_nonzero(b->cimg.as<uint8_t>(), b->frames, (int64_t)px, b->W, b->cnz.as<int32_t>(),
+                               (int64_t)b->ccap, b->cnzcount.as<int64_t>(), true, s));
+    }
+    HIP_TRY(hipEventRecord(b->cev[3], s));
+    b->clean_fresh = true;
+    if (sync) HIP_TRY(hipStreamSynchronize(s));
+    return SV_OK;
+}
+
+int sv_batch_road_clean_ms(sv_batch* b, float* kernel_ms, float* total_ms) {
+    if (!b) return fail(SV_E_ARG, "null batch");
+    if (!b->clean_fresh) return fail(SV_E_STATE, "no road clean-up (sv_batch_road_clean first)");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipEventSynchronize(b->cev[3]));
+    if (kernel_ms) HIP_TRY(hipEventElapsedTime(kernel_ms, b->cev[1], b->cev[2]));
+    if (total_ms) HIP_TRY(hipEventElapsedTime(total_ms, b->cev[0], b->cev[3]));
+    return SV_OK;
+}
+
+int sv_batch_read_road_clean(sv_batch* b, int frame, uint8_t* img, int32_t* nzpts, int64_t cap, int64_t* n) {
+    if (!b || frame < 0 || frame >= b->frames) return fail(SV_E_ARG, "bad args");
+    if (!b->clean_fresh) return fail(SV_E_STATE, "no road clean-up (sv_batch_road_clean first)");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    const size_t px = (size_t)b->H * b->W;
+    if (img)
+        HIP_TRY(hipMemcpy2D(img, b->Wu, b->cimg.as<uint8_t>() + px * frame, b->W, b->Wu, b->H, hipMemcpyDeviceToHost));
+    if (n) {
+        int64_t k = 0;
+        HIP_TRY(hipMemcpy(&k, b->cnzcount.as<int64_t>() + frame, sizeof k, hipMemcpyDeviceToHost));
+        *n = k;
+        if (k > cap) return fail(SV_E_CAP, "capacity %lld < %lld", (long long)cap, (long long)k);
+        if (k && nzpts) {
+            std::vector<uint32_t> pk((size_t)k);
+            HIP_TRY(hipMemcpy(pk.data(), b->cnz.as<uint32_t>() + b->ccap * frame, sizeof(uint32_t) * k,
+                              hipMemcpyDeviceToHost));
+            widen_walk(pk, nzpts);
         }
     }
     return SV_OK;
@@ -2444,9 +2635,9 @@ int sv_loop_create(int device, const sv_loop_params* prm, const sv_camera* cam, 
     *out = nullptr;
     const sv_loop_params& q = *prm;
     if (q.frames < 1 || q.slots < 1 || q.slots > 8 || (q.source != 0 && q.source != 1) || q.prepass < 0 ||
-        q.prepass > 2 || q.road < 0 || q.road > 2 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
+        q.prepass > 2 || q.road < 0 || q.road > 3 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
         return fail(SV_E_ARG, "sv_loop_create: bad parameters (frames >= 1, 1 <= slots <= 8, source 0/1, prepass "
-                              "0..2, road 0..2, step 1/2, trials >= 0, k >= 1)");
+                              "0..2, road 0..3, step 1/2, trials >= 0, k >= 1)");
     // what a submit would only find out after enqueueing the input and pre-pass stages (the RANSAC and synthetic
     // input limits of batch_ransac_prepare / sv_batch_synth)
     if (q.trials > 4096 || q.k > 1024) return fail(SV_E_ARG, "sv_loop_create: RANSAC trials <= 4096, k <= 1024");
@@ -2506,6 +2697,13 @@ int sv_loop_create(int device, const sv_loop_params* prm, const sv_camera* cam, 
 
 static int loop_flush(sv_loop* L);
 
+int sv_loop_road_mask(sv_loop* L, const uint8_t* mask) {
+    if (!L) return fail(SV_E_ARG, "sv_loop_road_mask: null loop");
+    for (sv_batch* b : L->slot)
+        if (int rc = sv_batch_road_mask(b, mask)) return rc;
+    return SV_OK;
+}
+
 // The batch the next sv_loop_submit processes (source 0: the caller fills it first); waits on the host until
 // the batch that last used its slot has finished every stage.
 int sv_loop_acquire(sv_loop* L, sv_batch** out) {
@@ -2564,6 +2762,9 @@ static int loop_enqueue_tail(sv_loop* L, int64_t seq, uint64_t gate_epoch) {
     HIP_TRY(begin(kLsRoad));
     if (q.road) {
         if (int rc = sv_batch_road_raster(b, 0)) return rc;
+    }
+    if (q.road == 3) {   // sanitiseRoadImage's clean-up of the images just made (functions.py:346-366)
+        if (int rc = sv_batch_road_clean(b, 0)) return rc;
     }
     HIP_TRY(end(kLsRoad));
     if (L->pending == seq) L->pending = -1;

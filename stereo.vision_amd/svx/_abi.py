@@ -62,12 +62,17 @@ SIGNATURES = {
     "sv_batch_read_disp": [P, I, P, P],
     "sv_road_raster": [P, I64, I, I, P],
     "sv_nonzero_points": [P, I, I, P, I64, PI64],
+    "sv_sanitise_road": [P, P, I, I, P, P, I64, PI64],
     "sv_batch_road_raster": [P, I],
     "sv_batch_nonzero": [P, I],
     "sv_batch_read_road": [P, I, P, P, I64, PI64],
     "sv_batch_road_map": [P, I],
     "sv_batch_road_bits": [P, I],
     "sv_batch_read_road_map": [P, I, P],
+    "sv_batch_road_mask": [P, P],
+    "sv_batch_road_clean": [P, I],
+    "sv_batch_read_road_clean": [P, I, P, P, I64, PI64],
+    "sv_batch_road_clean_ms": [P, PF, PF],
     "sv_point_errors": [P, I64, I64, P, P],
     "sv_hue_histogram": [P, I64, I64, P, P, P],
     "sv_select_less": [P, I64, D, P, PI64],
@@ -124,6 +129,7 @@ SIGNATURES = {
     "sv_gather_f64": [P, I64, I64, P, I64, I, I, P],
     "sv_loop_create": [I, ctypes.POINTER(LoopParams), ctypes.POINTER(Camera), P, ctypes.POINTER(P)],
     "sv_loop_destroy": [P],
+    "sv_loop_road_mask": [P, P],
     "sv_loop_acquire": [P, ctypes.POINTER(P)],
     "sv_loop_submit": [P, I64, PI64],
     "sv_loop_wait": [P, I64],

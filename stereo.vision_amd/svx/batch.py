@@ -262,6 +262,38 @@ class Batch:
         _abi.call("sv_batch_read_road", self._h, frame, _abi.ptr(img), _abi.ptr(pts), self.Ng, ctypes.byref(n))
         return img, pts[: n.value]
 
+    def road_mask(self, mask):
+        """The road_threshold_mask (H x W uint8, non-zero keeps a pixel) of road_clean(); None clears it to all
+        ones (sv_batch_road_mask)."""
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if m is not None and m.shape != (self.H, self.W):
+            raise ValueError(f"mask shape {m.shape} != {(self.H, self.W)}")
+        _abi.call("sv_batch_road_mask", self._h, _abi.ptr(m))
+
+    def road_clean(self, sync=True):
+        """sanitiseRoadImage's clean-up (functions.py:346-366: close 9 x 9, erode 17 x 17, AND mask, close 9 x 9)
+        of every frame's road image and the walk of the result, on the device; after road_raster()."""
+        _abi.call("sv_batch_road_clean", self._h, int(sync))
+
+    def road_clean_ms(self):
+        """(clean-up kernel ms, whole road_clean ms) of the last road_clean(), from device events."""
+        k, t = ctypes.c_float(0), ctypes.c_float(0)
+        _abi.call("sv_batch_road_clean_ms", self._h, ctypes.byref(k), ctypes.byref(t))
+        return float(k.value), float(t.value)
+
+    def read_road_clean(self, frame, walk=False):
+        """The cleaned road image of one frame (read_road() keeps returning the raw one); walk=True: also the
+        (K, 2) int32 [j, i] of its non-zero pixels in raster order."""
+        img = np.empty((self.H, self.W), np.uint8)
+        if not walk:
+            _abi.call("sv_batch_read_road_clean", self._h, frame, _abi.ptr(img), None, 0, None)
+            return img
+        n = ctypes.c_int64(0)
+        _abi.call("sv_batch_read_road_clean", self._h, frame, _abi.ptr(img), None, self.H * self.W, ctypes.byref(n))
+        pts = np.empty((max(n.value, 1), 2), np.int32)
+        _abi.call("sv_batch_read_road_clean", self._h, frame, None, _abi.ptr(pts), n.value, ctypes.byref(n))
+        return img, pts[: n.value]
+
     def ransac(self, seed_base, trials, k=600, first_frame=0, camera=None, sync=True):
         """RANSAC(maskpoints, trials) of every frame on the device (stereovision.py:84-94), frame F
         drawing what CPython draws after random.seed(seed_base + first_frame + F)."""

@@ -33,6 +33,9 @@ reference:
 * disparity stage (functions.py:61-128): ``gammaChange``, ``preProcessImages``,
   ``greyscale`` and ``disparity`` (StereoSGBM + filterSpeckles + scaling) —
   see svx/disparity.py.
+* ``sanitiseRoadImage(img, size)`` (functions.py:346-366): the road image's clean-up
+  (close, erode, mask, close; ParticleCleansing is the identity after them) and its pixel
+  walk; returns ``(img, np.matrix(pts))``. Installed only with ``install(.., morphology=True)``.
 * disparity pre-pass (functions.py:141-172): ``fillDisparity`` (new array, or
   the input itself when there is no previous frame), ``fillAltDisparity`` (in
   place, returns its argument), ``maskDisparity`` (new array; the mask is the
@@ -242,6 +245,47 @@ def nonzero_points(img):
     return out[: n.value]
 
 
+# ---------------------------------------------------------------------------
+# the road image's clean-up (functions.py:346-366)
+# ---------------------------------------------------------------------------
+def sanitise_road(img, mask=None):
+    """Array form of sanitiseRoadImage: (cleaned image (H, W) uint8 of 0 / 255, (K, 2) int32 [j, i] of its non-zero
+    pixels in raster order). The image's non-zero pixels are closed by 9 x 9, eroded by 17 x 17, ANDed with
+    mask != 0 (None: no mask) and closed by 9 x 9 again, OpenCV's default borders; ParticleCleansing changes
+    nothing after that (include/svx.h, sv_sanitise_road)."""
+    im = _as_u8(img, 2, "image")
+    if not im.flags.c_contiguous:
+        im = np.ascontiguousarray(im)
+    H, W = im.shape
+    m = None
+    if mask is not None:
+        m = np.ascontiguousarray(_as_u8(mask, 2, "mask"))
+        if m.shape != im.shape:
+            raise ValueError(f"mask shape {m.shape} != image shape {im.shape}")
+    out = np.empty((H, W), np.uint8)
+    n = ctypes.c_int64(0)
+    pts = np.empty((max(H * W, 1), 2), np.int32)
+    _abi.call("sv_sanitise_road", _abi.ptr(im), _abi.ptr(m), H, W, _abi.ptr(out), _abi.ptr(pts), H * W,
+              ctypes.byref(n))
+    return out, pts[: n.value].copy()
+
+
+def sanitiseRoadImage(img, size):  # noqa: N802
+    """functions.py:346-366 on the GPU, with the installed module's road_threshold_mask (functions.py:31): returns
+    (img, np.matrix(pts)) like the reference — the walk restricted to [0:height, 0:width] of `size`, an int64
+    (K, 2) matrix, or np.matrix([]) ((1, 0) float64) without points."""
+    if _module is None or getattr(_module, "road_threshold_mask", None) is None:
+        raise RuntimeError("sanitiseRoadImage needs the reference's road_threshold_mask: install(functions, "
+                           "morphology=True) first (or call sanitise_road(img, mask))")
+    (height, width) = size
+    out, pts = sanitise_road(img, _module.road_threshold_mask)
+    if height < out.shape[0] or width < out.shape[1]:
+        pts = pts[(pts[:, 0] < width) & (pts[:, 1] < height)]
+    if len(pts) == 0:
+        return out, np.matrix([])
+    return out, np.matrix(pts.astype(np.int64))
+
+
 # snake_case names used by BASELINE.json
 project_disparity_to_3d = projectDisparityTo3d
 project_3D_points_to_2D = project3DPointsTo2DImagePoints
@@ -264,13 +308,16 @@ PINNED = ("projectDisparityTo3d", "project3DPointsTo2DImagePoints", "fillAltDisp
 # (install(.., unpinned=True)).
 UNPINNED = ("disparity", "greyscale", "fillDisparity", "maskDisparity", "getImagePaths", "loadImages")
 PATCHED = PINNED + UNPINNED
+# sanitiseRoadImage (functions.py:346-366) restates cv2.morphologyEx / erode / bitwise_and and argues ParticleCleansing
+# away: unpinned like the above, and installed only with install(.., morphology=True).
+MORPHOLOGY = ("sanitiseRoadImage",)
 ALIASES = {"project_disparity_to_3d": "projectDisparityTo3d",
            "project_3D_points_to_2D": "project3DPointsTo2DImagePoints"}
 _saved = {}
 _ABSENT = object()
 
 
-def install(functions_module, unpinned=False):
+def install(functions_module, unpinned=False, morphology=False):
     """Patch the reference's `functions` module in place (stereovision.py resolves
     f.<name> at call time, so performStereoVision picks the GPU path up).
 
@@ -278,11 +325,13 @@ def install(functions_module, unpinned=False):
     reference's own on its fixtures. unpinned=True also replaces the UNPINNED ones, the
     restatements of OpenCV (SGBM, grey + equalizeHist, fillDisparity, maskDisparity, and
     getImagePaths / loadImages: cv2.imread of the PNG pairs, svx.io) whose equality with the
-    reference's cv2 cannot be checked here."""
+    reference's cv2 cannot be checked here. morphology=True also replaces
+    sanitiseRoadImage (MORPHOLOGY: the road image's 9 x 9 close / erode / mask / close and its
+    pixel walk, with the module's road_threshold_mask), a restatement of cv2 calls as well."""
     global _module
     _abi.lib()  # fail loudly now if libsvx is missing
     _module = functions_module
-    names = PINNED + (UNPINNED if unpinned else ()) + tuple(ALIASES)
+    names = PINNED + (UNPINNED if unpinned else ()) + (MORPHOLOGY if morphology else ()) + tuple(ALIASES)
     for name in names:
         if name not in _saved:
             _saved[name] = getattr(functions_module, name, _ABSENT)

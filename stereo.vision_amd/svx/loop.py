@@ -9,6 +9,8 @@ in batches and every batch runs the non-cv2 stages of that function:
              (two stages: the draw replay, the evaluation)
           -> the pipeline with each frame's own plane                   stereovision.py:97-113
           -> road raster + non-zero walk (+ imageRoadMap)               stereovision.py:131-156
+             (road="clean": + sanitiseRoadImage's clean-up and its walk, functions.py:346-366;
+              Batch.read_road_clean)
 
 FrameLoop keeps `slots` batches in flight, one HIP stream each; a stage of batch k waits for the same stage of
 batch k - 1 (a device event), and the RANSAC evaluation of batch k for batch k - 1's road pass, so with two slots
@@ -35,13 +37,13 @@ from .batch import CAMERA, Batch
 STAGES = ("input", "prepass", "maskpoints", "draw", "eval", "pipeline", "road")
 _SOURCES = {"caller": 0, "synth": 1}
 _PREPASS = {"none": 0, "previous": 1, "mean": 2}
-_ROAD = {"none": 0, "walk": 1, "map": 2}
+_ROAD = {"none": 0, "walk": 1, "map": 2, "clean": 3}
 
 
 class FrameLoop:
     def __init__(self, frames, H=544, W=1024, step=1, slots=2, source="synth", prepass="previous", trials=600,
                  k=600, seed_base=0, point_thr=0.05, hist_thr=10, road="walk", carmask=None, camera=None,
-                 device=0):
+                 device=0, road_mask=None):
         self.frames, self.H, self.W, self.step, self.slots, self.device = frames, H, W, step, slots, device
         prm = _abi.LoopParams(frames=frames, H=H, W=W, step=step, slots=slots, source=_SOURCES[source],
                               prepass=_PREPASS[prepass], trials=trials, k=k, seed_base=seed_base,
@@ -56,6 +58,20 @@ class FrameLoop:
                   ctypes.byref(h))
         self._h = h
         self._views = weakref.WeakSet()   # the Batch views handed out: invalidated by close()
+        if road_mask is not None:
+            try:
+                self.road_mask(road_mask)
+            except Exception:
+                self.close()
+                raise
+
+    def road_mask(self, mask):
+        """The road_threshold_mask of road="clean" (H x W uint8, non-zero keeps a pixel; None: all ones), for the
+        batches whose road stage is enqueued from now on (sv_loop_road_mask)."""
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if m is not None and m.shape != (self.H, self.W):
+            raise ValueError(f"road_mask shape {m.shape} != {(self.H, self.W)}")
+        _abi.call("sv_loop_road_mask", self._h, _abi.ptr(m))
 
     def _view(self, handle):
         v = Batch._view(handle, self.frames, self.H, self.W, self.step, self.device)
