@@ -133,6 +133,51 @@ int sv_nonzero_points(const uint8_t* img, int H, int W, int32_t* out, int64_t ca
 int sv_sanitise_road(const uint8_t* img, const uint8_t* mask, int H, int W, uint8_t* out_img, int32_t* out_pts,
                      int64_t cap, int64_t* out_n);
 
+/* ---- the obstacle stage (stereovision.py:170-189, functions.py:396-421) ---- */
+
+/* What the reference derives from the cleaned road image: cv2.convexHull(resultingPoints), the hull filled as a
+ * mask, obstacles = hull & ~road, getCenterPoint(hull) and getNormalVectorLine(centre, abc, disparity). The
+ * device works on the cleaned image as a bitmap (H rows of ceil(W / 32) words, pixel x at bit x & 31 of word
+ * x >> 5, pad bits zero, as csrc/svx_morph.h); the entry points below take and return u8 images.
+ *  - hull: the STRICT vertices of the convex hull of all set pixels (x, y) (no vertex collinear with its
+ *    neighbours), int32 (x, y) pairs, at most 2 H of them. Order: from the vertex with the smallest (y, then x)
+ *    down the left side with y increasing, then back up the right side; on each side the vertices have distinct
+ *    y apart from the top and bottom rows. No set pixel: n = 0; one pixel: n = 1; all pixels collinear: n = 2,
+ *    the two ends.
+ *  - hull mask: pixel (x, y) is set exactly when it lies in the closed hull, decided by exact integer
+ *    half-plane tests; per row that is every integer x with ceil(xl(y)) <= x <= floor(xr(y)), xl and xr the
+ *    rational crossings of the left and right chains (integer floor division, right for negative numerators).
+ *    For n <= 2 the mask is the lattice points of the point or segment.
+ *  - obstacles: hull mask & ~cleaned (stereovision.py:174-180, before the colouring).
+ *  - centre (cx, cy): the centre of the EXACT minimum enclosing circle of the hull's vertices, truncated toward
+ *    zero; n = 1: the point, n = 2: the midpoint truncated. The centre is a rational p / q with |q| < 2^26,
+ *    computed in 64-bit integers with 128-bit containment tests; bit 0 of `valid` is clear when n = 0, and
+ *    also, with n > 0 and the hull in place, should the circle's iteration reach its bound of 4 n + 64 exchanges
+ *    (it does not in exact arithmetic; the bound keeps a fault from spinning): then there is no centre and no tip.
+ *  - tip (tipx, tipy): getNormalVectorLine((cx, cy), abc, disparity) in fp64, the reference's operation order,
+ *    no contraction, truncated as int64. Bit 1 of `valid` is clear when there is no centre, no disparity or no
+ *    plane, when disparity[cy, cx] == 0, or when a result is not finite or does not fit an int64 (where the
+ *    reference raises inside its try).
+ * Parity with OpenCV (cv2 is absent here, as for sv_sanitise_road): cv2.convexHull's start vertex and
+ * orientation are unpinned (its consumers do not depend on them); cv2.drawContours(.., -100) also lights the
+ * Bresenham pixels of the hull's edges, which can lie outside the closed polygon by less than a pixel (in the
+ * reference they sit under the 5-pixel hull line drawRoadLine draws next); cv2.minEnclosingCircle is a float32
+ * approximation that depends on the version. getNormalVectorLine is pure Python and pinned by fixtures. */
+typedef struct {
+    int32_t n, cx, cy, valid;
+    int64_t tipx, tipy;
+} sv_hull_info;
+/* One host frame. cleaned: H x W u8, non-zero = road; disp (nullable): H x W u8; plane (nullable): abc; without
+ * disp or plane bit 1 of info->valid is clear. hull_pts: cap x 2 int32, SV_E_CAP (info->n set) when cap <
+ * info->n. hull_mask, obstacles (nullable): H x W u8 of 0 / 255. 2 <= W <= 4096, 1 <= H <= 4096. Synchronous. */
+int sv_road_obstacles(const uint8_t* cleaned, const uint8_t* disp, const sv_plane* plane, int H, int W,
+                      const sv_camera* cam, int32_t* hull_pts, int64_t cap, uint8_t* hull_mask, uint8_t* obstacles,
+                      sv_hull_info* info);
+/* The centre alone (functions.py:418-421 getCenterPoint with the exact circle): pts = n x 2 int32 (any points,
+ * |x|, |y| <= 16383, 1 <= n <= 8192: the circle is computed by one lane, so pass a hull, not a cloud),
+ * out_xy[2] = the centre truncated toward zero. */
+int sv_min_circle_centre(const int32_t* pts, int64_t n, int32_t* out_xy);
+
 /* ---- the stages a2-a6 one by one (the stage drop-ins) ---------------------- */
 
 /* calculatePointErrors (functions.py:300-312): out[i] = |(P_i . abc - 1) / d|
@@ -324,6 +369,19 @@ int sv_batch_read_road_clean(sv_batch* b, int frame, uint8_t* img, int32_t* nzpt
 /* ms of the last sv_batch_road_clean from HIP events on the batch stream: *kernel_ms the clean-up kernel alone,
  * *total_ms the whole call's device work (pack, clean-up, image + walk). Synchronises the batch stream. */
 int sv_batch_road_clean_ms(sv_batch* b, float* kernel_ms, float* total_ms);
+/* The obstacle stage (sv_road_obstacles) of every frame's cleaned image, on the device: one kernel that reads the
+ * clean-up's bitmaps. SV_E_STATE unless a clean-up is current (sv_batch_road_clean after the last road pass); any
+ * call that invalidates the clean-up invalidates the hull too. disparity = the batch's cleaned, unmasked frames
+ * (what sv_batch_read_disp returns); abc = the plane the frame's last pipeline call used: the frame's own RANSAC
+ * plane (sv_batch_pipeline_planes; none found: bit 1 of valid clear), else the call's shared plane.
+ * 1 <= H <= 4096. */
+int sv_batch_road_hull(sv_batch* b, int sync);
+/* One frame's results; every pointer is nullable. hull_pts: cap x 2 int32 (SV_E_CAP, info->n set, when cap <
+ * n); hull_mask, obstacles: H x W u8 of 0 / 255. */
+int sv_batch_read_road_hull(sv_batch* b, int frame, int32_t* hull_pts, int64_t cap, uint8_t* hull_mask,
+                            uint8_t* obstacles, sv_hull_info* info);
+/* ms of the last sv_batch_road_hull from HIP events on the batch stream. Synchronises the batch stream. */
+int sv_batch_road_hull_ms(sv_batch* b, float* ms);
 
 /* Batched RANSAC (stereovision.py:84-94 for every frame):
  * maskpoints = the fp64 step-2 projection of the batch's disparity under the
@@ -444,7 +502,9 @@ typedef struct {
     double point_thr;    /* computePlanarThreshold threshold (0.05)                                    */
     int hist_thr;        /* filterPointsByHistogram threshold (10)                                     */
     int road;            /* 0 none, 1 road raster + walk, 2 + imageRoadMap, 3 road raster + walk + the
-                            clean-up (sv_batch_road_clean; its mask: sv_loop_road_mask)                 */
+                            clean-up (sv_batch_road_clean; its mask: sv_loop_road_mask), 4 all of 3 + the
+                            obstacle stage (sv_batch_road_hull; results: sv_batch_read_road_hull of the
+                            batch sv_loop_batch returns), inside the timeline's "road" stage           */
 } sv_loop_params;
 typedef struct sv_loop sv_loop;
 /* carmask: the grey H x W mask of maskDisparity (functions.py:35, :169-172), NULL for none. */

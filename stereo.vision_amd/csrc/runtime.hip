@@ -16,6 +16,8 @@
 
 #include "../../include/svx.h"
 #include "svx_launch.h"
+#include "svx_hull.h"
+#include "svx_hull_host.h"
 #include "svx_morph.h"
 #include "svx_sgbm.h"
 
@@ -150,6 +152,7 @@ struct Device {
     // drop-in scratch
     DevBuf disp, bgr, xyz, rgb, ctrl, xy, aux, aux2;
     DevBuf mbits;                     // sv_sanitise_road: the image, the cleaned image and the mask as bitmaps
+    DevBuf hull;                      // sv_road_obstacles: bitmaps, vertices and info (HullLayout)
     DevBuf sg_l, sg_r, sg_out, sg_filt, sg_hist;   // host-frame SGBM / grey drop-ins
     SgbmBufs sg;
     Tables tables;
@@ -298,6 +301,14 @@ struct sv_batch {
     bool clean_fresh = false;   // cimg / cnz hold the clean-up of the current road images
     size_t ccap = 0;            // walk entries per frame of cnz: H x Wu rounded up to 64
     hipEvent_t cev[4] = {nullptr, nullptr, nullptr, nullptr};   // start, clean-up kernel's start / end, end
+    // the obstacle stage (sv_batch_road_hull): hull masks, obstacles, vertices and infos (HullLayout); the planes
+    // of the last pipeline call (device planes at a stride, else the shared host plane) for the glyph tip
+    DevBuf hbuf;
+    bool hull_fresh = false;    // hbuf holds the obstacle stage of the current clean-up (reset by every clean-up)
+    hipEvent_t hev[2] = {nullptr, nullptr};
+    const FramePlane* hull_planes = nullptr;
+    int hull_plane_stride = 0;
+    HullPlane hull_shared{};
     DevBuf mpts, rres;          // one frame's maskpoints as fp64 (read-back scratch); counts + batched RANSAC results
     DevBuf prev0buf, rdbuf;     // the host prev0 of sv_batch_prepass; sv_batch_read_disp's masked frame (batch-owned:
                                 // the device-wide drop-in scratch is used on other streams)
@@ -642,7 +653,7 @@ int sv_batch_destroy(sv_batch* b) {
                       &b->carmask, &b->road, &b->rmap, &b->nz, &b->nzcount, &b->mpts, &b->mpk, &b->rres, &b->rtab, &b->rtrace, &b->fplanes, &b->dplane, &b->abc,
                       &b->pairL, &b->pairR, &b->rsidx, &b->rtri, &b->bgrL, &b->bgrR,
                       &b->glut, &b->ghist, &b->sgflags, &b->prev0buf, &b->rdbuf, &b->rbits, &b->roff, &b->raw, &b->rmask, &b->cpack,
-                      &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff})
+                      &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff, &b->hbuf})
         if (x->p) (void)hipFree(x->p);
     if (b->hcnt) (void)hipHostFree(b->hcnt);
     if (b->cnt_ev) (void)hipEventDestroy(b->cnt_ev);
@@ -650,6 +661,8 @@ int sv_batch_destroy(sv_batch* b) {
     for (auto& ev : b->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->cev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : b->hev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->pool) (void)hipEventDestroy(ev);
     for (auto& ev : b->sync_ev) (void)hipEventDestroy(ev);
@@ -946,6 +959,10 @@ static int batch_pipeline_impl(sv_batch* b, const sv_camera* cam, const sv_plane
     }
     b->rbits_fresh = false;
     b->road_fresh = b->clean_fresh = false;   // the road images no longer belong to the points
+    // the glyph tip of the obstacle stage takes this call's planes (sv_batch_road_hull)
+    b->hull_planes = planes;
+    b->hull_plane_stride = planes ? plane_stride : 0;
+    b->hull_shared = HullPlane{plane->a, plane->b, plane->c, p.f, p.fB, p.cw, p.ch, planes ? 0u : 1u};
     if (mode >= 2 && b->road_bits && resident_road_bits_supported(p)) {   // the road bitmap too (sv_batch_road_bits)
         HIP_TRY(b->rbits.ensure(sizeof(uint32_t) * 32 * (size_t)b->H * b->frames));
         bf.rbits = b->rbits.as<uint32_t>();
@@ -1655,7 +1672,7 @@ int sv_batch_road_clean(sv_batch* b, int sync) {
     const size_t px = (size_t)H * b->W, words = (size_t)H * WW;
     for (hipEvent_t& e : b->cev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    b->clean_fresh = false;
+    b->clean_fresh = b->hull_fresh = false;
     b->ccap = ((size_t)H * Wu + 63) / 64 * 64;
     HIP_TRY(b->cbits.ensure(sizeof(uint32_t) * words * b->frames));
     HIP_TRY(b->cimg.ensure(px * b->frames));
@@ -1719,6 +1736,156 @@ int sv_batch_read_road_clean(sv_batch* b, int frame, uint8_t* img, int32_t* nzpt
                               hipMemcpyDeviceToHost));
             widen_walk(pk, nzpts);
         }
+    }
+    return SV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the obstacle stage (stereovision.py:170-189, functions.py:396-421): kernels/hull.hip
+// ---------------------------------------------------------------------------
+static_assert(kHullHostMaxH == kHullMaxH, "svx_hull_host.h and svx_hull.h disagree");
+
+int sv_road_obstacles(const uint8_t* cleaned, const uint8_t* disp, const sv_plane* plane, int H, int W,
+                      const sv_camera* cam, int32_t* hull_pts, int64_t cap, uint8_t* hull_mask, uint8_t* obstacles,
+                      sv_hull_info* info) {
+    if (const char* why = hull_check_args(cleaned, cam, H, W, hull_pts, cap, info))
+        return fail(SV_E_ARG, "sv_road_obstacles: bad arguments (%s)", why);
+    *info = sv_hull_info{0, 0, 0, 0, 0, 0};
+    int dev;
+    if (int rc = current_device(&dev)) return rc;
+    Device* d;
+    if (int rc = dev_get(dev, &d)) return rc;
+    std::lock_guard<std::mutex> lk(d->mu);
+    hipStream_t s = d->stream;
+    const HullLayout l = hull_layout(H, W, 1, true);
+    HIP_TRY(d->hull.ensure(l.bytes));
+    char* base = d->hull.as<char>();
+    uint32_t* bin = reinterpret_cast<uint32_t*>(base + l.off_in);
+    uint32_t* bmask = reinterpret_cast<uint32_t*>(base + l.off_mask);
+    uint32_t* bobst = reinterpret_cast<uint32_t*>(base + l.off_obst);
+    int32_t* dpts = reinterpret_cast<int32_t*>(base + l.off_pts);
+    sv_hull_info* dinfo = reinterpret_cast<sv_hull_info*>(base + l.off_info);
+    if (int rc = upload_u8(d->aux, cleaned, H, W, l.pitch, s)) return rc;
+    HIP_TRY(launch_morph_pack(d->aux.as<uint8_t>(), (int64_t)l.px, l.pitch, W, H, 1, bin, s));
+    const uint8_t* ddisp = nullptr;
+    HullPlane hp{};
+    if (disp && plane) {
+        if (int rc = upload_u8(d->disp, disp, H, W, l.pitch, s)) return rc;
+        ddisp = d->disp.as<uint8_t>();
+        hp = HullPlane{plane->a, plane->b, plane->c, cam->f, cam->f * cam->B, cam->cw, cam->ch, 1u};
+    }
+    HIP_TRY(launch_road_hull(bin, 1, H, W, ddisp, (int64_t)l.px, l.pitch, nullptr, 0, hp, dpts,
+                             hull_mask ? bmask : nullptr, obstacles ? bobst : nullptr, dinfo, s));
+    // the images (into aux / aux2: the pack above has read aux, in stream order)
+    if (hull_mask) {
+        HIP_TRY(launch_morph_unpack(bmask, 1, H, W, l.pitch, d->aux.as<uint8_t>(), s));
+        HIP_TRY(hipMemcpy2DAsync(hull_mask, W, d->aux.p, l.pitch, W, H, hipMemcpyDeviceToHost, s));
+    }
+    if (obstacles) {
+        HIP_TRY(d->aux2.ensure(l.px));
+        HIP_TRY(launch_morph_unpack(bobst, 1, H, W, l.pitch, d->aux2.as<uint8_t>(), s));
+        HIP_TRY(hipMemcpy2DAsync(obstacles, W, d->aux2.p, l.pitch, W, H, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipMemcpyAsync(info, dinfo, sizeof *info, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (info->n > cap && hull_pts)
+        return fail(SV_E_CAP, "capacity %lld < %d hull vertices", (long long)cap, info->n);
+    if (hull_pts && info->n > 0) {
+        HIP_TRY(hipMemcpyAsync(hull_pts, dpts, sizeof(int32_t) * 2 * (size_t)info->n, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+    }
+    return SV_OK;
+}
+
+int sv_min_circle_centre(const int32_t* pts, int64_t n, int32_t* out_xy) {
+    if (!pts || !out_xy || n < 1 || n > kCircleMaxPoints)
+        return fail(SV_E_ARG, "sv_min_circle_centre: bad arguments (1 <= n <= %d)", kCircleMaxPoints);
+    for (int64_t i = 0; i < 2 * n; ++i)
+        if (pts[i] < -kHullMaxCoord || pts[i] > kHullMaxCoord)
+            return fail(SV_E_RANGE, "sv_min_circle_centre: coordinate %d outside +-%d", pts[i], kHullMaxCoord);
+    int dev;
+    if (int rc = current_device(&dev)) return rc;
+    Device* d;
+    if (int rc = dev_get(dev, &d)) return rc;
+    std::lock_guard<std::mutex> lk(d->mu);
+    hipStream_t s = d->stream;
+    HIP_TRY(d->xy.ensure(sizeof(int32_t) * 2 * (size_t)n));
+    HIP_TRY(d->hull.ensure(16));
+    HIP_TRY(hipMemcpyAsync(d->xy.p, pts, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_min_circle(d->xy.as<int32_t>(), n, d->hull.as<int32_t>(), s));
+    int32_t out[3] = {0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(out, d->hull.p, sizeof out, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (!out[2]) return fail(SV_E_DEVICE, "sv_min_circle_centre: the circle's iteration did not end");
+    out_xy[0] = out[0];
+    out_xy[1] = out[1];
+    return SV_OK;
+}
+
+int sv_batch_road_hull(sv_batch* b, int sync) {
+    if (!b) return fail(SV_E_ARG, "null batch");
+    if (!b->clean_fresh) return fail(SV_E_STATE, "no current road clean-up (sv_batch_road_clean first)");
+    if (b->H < 1 || b->H > kHullMaxH) return fail(SV_E_ARG, "the obstacle stage takes frames of 1..4096 rows");
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    for (hipEvent_t& e : b->hev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    b->hull_fresh = false;
+    const HullLayout l = hull_layout(b->H, b->Wu, b->frames, false);
+    HIP_TRY(b->hbuf.ensure(l.bytes));
+    char* base = b->hbuf.as<char>();
+    HIP_TRY(hipEventRecord(b->hev[0], s));
+    HIP_TRY(launch_road_hull(b->cbits.as<uint32_t>(), b->frames, b->H, b->Wu, b->disp.as<uint8_t>(),
+                             (int64_t)b->H * b->W, b->W, b->hull_planes, b->hull_plane_stride, b->hull_shared,
+                             reinterpret_cast<int32_t*>(base + l.off_pts),
+                             reinterpret_cast<uint32_t*>(base + l.off_mask),
+                             reinterpret_cast<uint32_t*>(base + l.off_obst),
+                             reinterpret_cast<sv_hull_info*>(base + l.off_info), s));
+    HIP_TRY(hipEventRecord(b->hev[1], s));
+    b->hull_fresh = true;
+    if (sync) HIP_TRY(hipStreamSynchronize(s));
+    return SV_OK;
+}
+
+int sv_batch_road_hull_ms(sv_batch* b, float* ms) {
+    if (!b || !ms) return fail(SV_E_ARG, "null batch or ms");
+    if (!b->clean_fresh || !b->hull_fresh) return fail(SV_E_STATE, "no obstacle stage (sv_batch_road_hull first)");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipEventSynchronize(b->hev[1]));
+    HIP_TRY(hipEventElapsedTime(ms, b->hev[0], b->hev[1]));
+    return SV_OK;
+}
+
+int sv_batch_read_road_hull(sv_batch* b, int frame, int32_t* hull_pts, int64_t cap, uint8_t* hull_mask,
+                            uint8_t* obstacles, sv_hull_info* info) {
+    if (!b || frame < 0 || frame >= b->frames || cap < 0) return fail(SV_E_ARG, "bad args");
+    if (!b->clean_fresh || !b->hull_fresh) return fail(SV_E_STATE, "no obstacle stage (sv_batch_road_hull first)");
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    const HullLayout l = hull_layout(b->H, b->Wu, b->frames, false);
+    const char* base = b->hbuf.as<char>();
+    const size_t px = (size_t)b->H * b->W;
+    uint8_t* imgs[2] = {hull_mask, obstacles};
+    const size_t offs[2] = {l.off_mask, l.off_obst};
+    if (hull_mask || obstacles) HIP_TRY(b->rdbuf.ensure(2 * px));
+    for (int k = 0; k < 2; ++k)
+        if (imgs[k])
+            HIP_TRY(launch_morph_unpack(reinterpret_cast<const uint32_t*>(base + offs[k]) + l.words * frame, 1, b->H,
+                                        b->Wu, b->W, b->rdbuf.as<uint8_t>() + px * k, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int k = 0; k < 2; ++k)
+        if (imgs[k])
+            HIP_TRY(hipMemcpy2D(imgs[k], b->Wu, b->rdbuf.as<uint8_t>() + px * k, b->W, b->Wu, b->H,
+                                hipMemcpyDeviceToHost));
+    sv_hull_info hi;
+    HIP_TRY(hipMemcpy(&hi, reinterpret_cast<const sv_hull_info*>(base + l.off_info) + frame, sizeof hi,
+                      hipMemcpyDeviceToHost));
+    if (info) *info = hi;
+    if (hull_pts) {
+        if (hi.n > cap) return fail(SV_E_CAP, "capacity %lld < %d hull vertices", (long long)cap, hi.n);
+        if (hi.n > 0)
+            HIP_TRY(hipMemcpy(hull_pts, reinterpret_cast<const int32_t*>(base + l.off_pts) + 4 * (size_t)b->H * frame,
+                              sizeof(int32_t) * 2 * (size_t)hi.n, hipMemcpyDeviceToHost));
     }
     return SV_OK;
 }
@@ -2635,9 +2802,9 @@ int sv_loop_create(int device, const sv_loop_params* prm, const sv_camera* cam, 
     *out = nullptr;
     const sv_loop_params& q = *prm;
     if (q.frames < 1 || q.slots < 1 || q.slots > 8 || (q.source != 0 && q.source != 1) || q.prepass < 0 ||
-        q.prepass > 2 || q.road < 0 || q.road > 3 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
+        q.prepass > 2 || q.road < 0 || q.road > 4 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
         return fail(SV_E_ARG, "sv_loop_create: bad parameters (frames >= 1, 1 <= slots <= 8, source 0/1, prepass "
-                              "0..2, road 0..3, step 1/2, trials >= 0, k >= 1)");
+                              "0..2, road 0..4, step 1/2, trials >= 0, k >= 1)");
     // what a submit would only find out after enqueueing the input and pre-pass stages (the RANSAC and synthetic
     // input limits of batch_ransac_prepare / sv_batch_synth)
     if (q.trials > 4096 || q.k > 1024) return fail(SV_E_ARG, "sv_loop_create: RANSAC trials <= 4096, k <= 1024");
@@ -2763,8 +2930,11 @@ static int loop_enqueue_tail(sv_loop* L, int64_t seq, uint64_t gate_epoch) {
     if (q.road) {
         if (int rc = sv_batch_road_raster(b, 0)) return rc;
     }
-    if (q.road == 3) {   // sanitiseRoadImage's clean-up of the images just made (functions.py:346-366)
+    if (q.road >= 3) {   // sanitiseRoadImage's clean-up of the images just made (functions.py:346-366)
         if (int rc = sv_batch_road_clean(b, 0)) return rc;
+    }
+    if (q.road == 4) {   // the obstacle stage on the cleaned images (stereovision.py:170-189)
+        if (int rc = sv_batch_road_hull(b, 0)) return rc;
     }
     HIP_TRY(end(kLsRoad));
     if (L->pending == seq) L->pending = -1;

@@ -34,6 +34,12 @@ class LoopParams(ctypes.Structure):
                 ("point_thr", ctypes.c_double), ("hist_thr", ctypes.c_int), ("road", ctypes.c_int)]
 
 
+class HullInfo(ctypes.Structure):
+    """sv_hull_info (include/svx.h)."""
+    _fields_ = [("n", ctypes.c_int32), ("cx", ctypes.c_int32), ("cy", ctypes.c_int32), ("valid", ctypes.c_int32),
+                ("tipx", ctypes.c_int64), ("tipy", ctypes.c_int64)]
+
+
 P = ctypes.c_void_p
 I = ctypes.c_int
 I64 = ctypes.c_int64
@@ -63,6 +69,9 @@ SIGNATURES = {
     "sv_road_raster": [P, I64, I, I, P],
     "sv_nonzero_points": [P, I, I, P, I64, PI64],
     "sv_sanitise_road": [P, P, I, I, P, P, I64, PI64],
+    "sv_road_obstacles": [P, P, ctypes.POINTER(Plane), I, I, ctypes.POINTER(Camera), P, I64, P, P,
+                          ctypes.POINTER(HullInfo)],
+    "sv_min_circle_centre": [P, I64, P],
     "sv_batch_road_raster": [P, I],
     "sv_batch_nonzero": [P, I],
     "sv_batch_read_road": [P, I, P, P, I64, PI64],
@@ -73,6 +82,9 @@ SIGNATURES = {
     "sv_batch_road_clean": [P, I],
     "sv_batch_read_road_clean": [P, I, P, P, I64, PI64],
     "sv_batch_road_clean_ms": [P, PF, PF],
+    "sv_batch_road_hull": [P, I],
+    "sv_batch_read_road_hull": [P, I, P, I64, P, P, ctypes.POINTER(HullInfo)],
+    "sv_batch_road_hull_ms": [P, PF],
     "sv_point_errors": [P, I64, I64, P, P],
     "sv_hue_histogram": [P, I64, I64, P, P, P],
     "sv_select_less": [P, I64, D, P, PI64],
@@ -193,6 +205,20 @@ def device_count():
     n = ctypes.c_int(0)
     rc = lib().sv_device_count(ctypes.byref(n))
     return n.value if rc == 0 else 0
+
+
+def hull_result(H, W, images, read):
+    """The dict dropin.road_obstacles and Batch.read_road_hull return, from read(pts, cap, hull_mask, obstacles,
+    info), a call of sv_road_obstacles / sv_batch_read_road_hull."""
+    import numpy as np
+    info = HullInfo()
+    pts = np.empty((2 * H, 2), np.int32)
+    mask = np.empty((H, W), np.uint8) if images else None
+    obst = np.empty((H, W), np.uint8) if images else None
+    read(pts, 2 * H, mask, obst, ctypes.byref(info))
+    return {"hull": pts[: info.n].reshape(-1, 1, 2).copy(), "hull_mask": mask, "obstacles": obst,
+            "centre": (int(info.cx), int(info.cy)) if info.valid & 1 else None,
+            "tip": (int(info.tipx), int(info.tipy)) if info.valid & 2 else None, "valid": int(info.valid)}
 
 
 class _PinnedPool:

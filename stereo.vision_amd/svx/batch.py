@@ -294,6 +294,24 @@ class Batch:
         _abi.call("sv_batch_read_road_clean", self._h, frame, None, _abi.ptr(pts), n.value, ctypes.byref(n))
         return img, pts[: n.value]
 
+    def road_hull(self, sync=True):
+        """The obstacle stage (stereovision.py:170-189) of every frame's cleaned road image, on the device: the
+        convex hull, the hull mask, the obstacles, the hull's circle centre and the glyph tip; after road_clean()."""
+        _abi.call("sv_batch_road_hull", self._h, int(sync))
+
+    def road_hull_ms(self):
+        """ms of the last road_hull(), from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_road_hull_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
+    def read_road_hull(self, frame, images=True):
+        """One frame's obstacle stage: {"hull": (n, 1, 2) int32 (cv2.convexHull's shape), "hull_mask", "obstacles":
+        (H, W) uint8 of 0 / 255 (None with images=False), "centre": (cx, cy) or None, "tip": (x, y) or None,
+        "valid": the flags}."""
+        return _abi.hull_result(self.H, self.W, images, lambda pts, cap, m, o, info: _abi.call(
+            "sv_batch_read_road_hull", self._h, frame, _abi.ptr(pts), cap, _abi.ptr(m), _abi.ptr(o), info))
+
     def ransac(self, seed_base, trials, k=600, first_frame=0, camera=None, sync=True):
         """RANSAC(maskpoints, trials) of every frame on the device (stereovision.py:84-94), frame F
         drawing what CPython draws after random.seed(seed_base + first_frame + F)."""

@@ -36,6 +36,9 @@ reference:
 * ``sanitiseRoadImage(img, size)`` (functions.py:346-366): the road image's clean-up
   (close, erode, mask, close; ParticleCleansing is the identity after them) and its pixel
   walk; returns ``(img, np.matrix(pts))``. Installed only with ``install(.., morphology=True)``.
+* ``getCenterPoint(points)`` (functions.py:418-421): the centre of the exact minimum enclosing
+  circle; installed only with ``install(.., hull=True)``. ``road_obstacles`` gives the whole
+  obstacle stage (hull, hull mask, obstacles, centre, glyph tip) of a cleaned road image.
 * disparity pre-pass (functions.py:141-172): ``fillDisparity`` (new array, or
   the input itself when there is no previous frame), ``fillAltDisparity`` (in
   place, returns its argument), ``maskDisparity`` (new array; the mask is the
@@ -286,6 +289,51 @@ def sanitiseRoadImage(img, size):  # noqa: N802
     return out, np.matrix(pts.astype(np.int64))
 
 
+# ---------------------------------------------------------------------------
+# the obstacle stage (stereovision.py:170-189, functions.py:396-421)
+# ---------------------------------------------------------------------------
+def road_obstacles(cleaned, disparity=None, abc=None, camera=None):
+    """What stereovision.py:170-189 and :198-204 derive from the cleaned road image (non-zero = road), on the GPU:
+    {"hull": (n, 1, 2) int32, the strict vertices of the convex hull of the road pixels (cv2.convexHull's shape; from
+    the top-left vertex down the left side and back up the right side), "hull_mask": the closed hull filled, 0 / 255,
+    "obstacles": hull_mask & ~cleaned, "centre": the centre of the hull's exact minimum enclosing circle truncated
+    (None without road pixels), "tip": getNormalVectorLine(centre, abc, disparity) (None without disparity or abc,
+    or where the reference raises), "valid": the flags} (include/svx.h, sv_road_obstacles)."""
+    im = np.ascontiguousarray(_as_u8(cleaned, 2, "image"))
+    H, W = im.shape
+    dp = None
+    if disparity is not None:
+        dp = np.ascontiguousarray(_as_u8(disparity, 2, "disparity"))
+        if dp.shape != im.shape:
+            raise ValueError(f"disparity shape {dp.shape} != image shape {im.shape}")
+    pl = None
+    if abc is not None:
+        a, b, c = (float(v) for v in np.asarray(abc, np.float64).reshape(-1)[:3])
+        pl = ctypes.byref(_abi.Plane(a, b, c))
+    cam = _abi.Camera(*camera) if camera is not None else _camera()
+    return _abi.hull_result(H, W, True, lambda pts, cap, m, o, info: _abi.call(
+        "sv_road_obstacles", _abi.ptr(im), _abi.ptr(dp), pl, H, W, ctypes.byref(cam), _abi.ptr(pts), cap,
+        _abi.ptr(m), _abi.ptr(o), info))
+
+
+def getCenterPoint(points):  # noqa: N802
+    """functions.py:418-421 with the exact circle: (int(x), int(y)) of the centre of the minimum enclosing circle of
+    any (n, 1, 2) or (n, 2) integer points (|coordinate| <= 16383, at most 8192 distinct ones), computed in integers on the GPU. The reference's
+    cv2.minEnclosingCircle is a float32 approximation: installed only with install(.., hull=True)."""
+    p = np.asarray(points)
+    if p.dtype.kind not in "iu" or p.size == 0 or p.size % 2:
+        raise TypeError("getCenterPoint takes a non-empty (n, 1, 2) or (n, 2) integer array")
+    p = np.unique(p.reshape(-1, 2).astype(np.int64), axis=0)     # duplicates do not move the circle
+    if len(p) > 8192:
+        raise ValueError("getCenterPoint takes at most 8192 distinct points (a hull, not a cloud)")
+    if np.abs(p).max() > 16383:
+        raise ValueError("getCenterPoint: coordinates beyond +-16383")
+    p = p.astype(np.int32)
+    out = np.zeros(2, np.int32)
+    _abi.call("sv_min_circle_centre", _abi.ptr(p), len(p), _abi.ptr(out))
+    return (int(out[0]), int(out[1]))
+
+
 # snake_case names used by BASELINE.json
 project_disparity_to_3d = projectDisparityTo3d
 project_3D_points_to_2D = project3DPointsTo2DImagePoints
@@ -311,13 +359,16 @@ PATCHED = PINNED + UNPINNED
 # sanitiseRoadImage (functions.py:346-366) restates cv2.morphologyEx / erode / bitwise_and and argues ParticleCleansing
 # away: unpinned like the above, and installed only with install(.., morphology=True).
 MORPHOLOGY = ("sanitiseRoadImage",)
+# getCenterPoint (functions.py:418-421) returns the exact circle's centre where cv2.minEnclosingCircle approximates
+# in float32 (which way depends on its version): unpinned too, installed only with install(.., hull=True).
+HULL = ("getCenterPoint",)
 ALIASES = {"project_disparity_to_3d": "projectDisparityTo3d",
            "project_3D_points_to_2D": "project3DPointsTo2DImagePoints"}
 _saved = {}
 _ABSENT = object()
 
 
-def install(functions_module, unpinned=False, morphology=False):
+def install(functions_module, unpinned=False, morphology=False, hull=False):
     """Patch the reference's `functions` module in place (stereovision.py resolves
     f.<name> at call time, so performStereoVision picks the GPU path up).
 
@@ -327,11 +378,13 @@ def install(functions_module, unpinned=False, morphology=False):
     getImagePaths / loadImages: cv2.imread of the PNG pairs, svx.io) whose equality with the
     reference's cv2 cannot be checked here. morphology=True also replaces
     sanitiseRoadImage (MORPHOLOGY: the road image's 9 x 9 close / erode / mask / close and its
-    pixel walk, with the module's road_threshold_mask), a restatement of cv2 calls as well."""
+    pixel walk, with the module's road_threshold_mask), a restatement of cv2 calls as well;
+    hull=True also replaces getCenterPoint (HULL) by the exact circle's centre."""
     global _module
     _abi.lib()  # fail loudly now if libsvx is missing
     _module = functions_module
-    names = PINNED + (UNPINNED if unpinned else ()) + (MORPHOLOGY if morphology else ()) + tuple(ALIASES)
+    names = PINNED + (UNPINNED if unpinned else ()) + (MORPHOLOGY if morphology else ()) + \
+        (HULL if hull else ()) + tuple(ALIASES)
     for name in names:
         if name not in _saved:
             _saved[name] = getattr(functions_module, name, _ABSENT)
