@@ -178,6 +178,38 @@ int sv_road_obstacles(const uint8_t* cleaned, const uint8_t* disp, const sv_plan
  * out_xy[2] = the centre truncated toward zero. */
 int sv_min_circle_centre(const int32_t* pts, int64_t n, int32_t* out_xy);
 
+/* ---- the result image (stereovision.py:181-209, functions.py:390-394, :424-431) ---- */
+
+/* The picture performStereoVision shows per frame: the left image dimmed with its obstacles tinted yellow
+ * (cv2.addWeighted), the road hull outlined in red (drawRoadLine) and the road-normal glyph drawn from the hull's
+ * centre (drawNormalLine). Inputs: the BGR, the obstacle image, the hull's n vertices in outline order and the
+ * sv_hull_info of the obstacle stage (centre, tip, valid). Output: H x W x 3 u8, (B, G, R) per pixel.
+ * Every predicate is exact integer arithmetic on pixel coordinates p = (x, y); D(p; a, b) is the squared Euclidean
+ * distance from p to the closed segment ab (a point when a = b). Later layers overwrite earlier ones:
+ *  0. n = 0 (the reference's cv2.convexHull raises inside both try blocks): the BGR unchanged.
+ *  1. overlay, n >= 1: every channel value i becomes rint(0.6 i) = floor((6 i + 5) / 10); on obstacle pixels G and
+ *     R get 102 more. This is cv2.addWeighted(obst, 0.4, img, 0.6, 0) with obst in {0, 255}: 3 i / 5 is never a
+ *     tie, the fp32 error is about 1e-5 and the maximum is 255, so every evaluation order gives the same byte.
+ *  2. hull outline, n >= 1, whatever `valid` says: (0, 0, 255) where 4 D(p; v_k, v_k+1) <= 25 for some edge of the
+ *     closed polygon v_0 .. v_n-1 -> v_0 in the stored order; n = 1: the 21 pixels with dx^2 + dy^2 <= 6; n = 2:
+ *     the one segment.
+ *  3. glyph line, when bit 1 of `valid` is set and |tipx|, |tipy| <= 2^31 - 1 (cv2 takes no larger point, and the
+ *     reference's try swallows the error): (204, 185, 22) where D(p; centre, tip) <= 1.
+ *  4. glyph head, under the same condition: (214, 195, 32) where |p - tip|^2 <= 49 (cv2.circle with radius 2 and
+ *     thickness 10 covers radii 0-7).
+ * Strokes are clipped to the image; a tip far outside still draws the visible part of its line.
+ * Parity with OpenCV: layer 1 is pinned (tests/test_result_cpu.py: all 512 (obst, i) pairs under four fp32
+ * evaluation orders). Layers 2-4 are unpinned: cv2 is absent here, and its thick line is a fixed-point polygon with
+ * round caps whose rim pixels depend on the version; the capsule and the disc above are the shapes it approximates.
+ * The vertices must be a convex polygon in outline order (either orientation; what sv_road_obstacles returns):
+ * the device plans the outline as at most two pixel runs a row. */
+/* One host frame, synchronous. bgr: H x W x 3 u8; obstacles: H x W u8, non-zero = obstacle; hull_pts: n x 2 int32
+ * (x, y), 0 <= n <= 8192, |coordinate| <= 16383; info (nullable = no glyph): cx, cy, valid, tipx, tipy are read
+ * (|cx|, |cy| <= 16383 when bit 1 of valid is set), info->n is not; out: H x W x 3 u8, not overlapping bgr.
+ * 2 <= W <= 4096, 1 <= H <= 4096. SV_E_ARG for anything else, a polygon that is not convex included. */
+int sv_result_image(const uint8_t* bgr, const uint8_t* obstacles, const int32_t* hull_pts, int64_t n,
+                    const sv_hull_info* info, int H, int W, uint8_t* out);
+
 /* ---- the stages a2-a6 one by one (the stage drop-ins) ---------------------- */
 
 /* calculatePointErrors (functions.py:300-312): out[i] = |(P_i . abc - 1) / d|
@@ -382,6 +414,17 @@ int sv_batch_read_road_hull(sv_batch* b, int frame, int32_t* hull_pts, int64_t c
                             uint8_t* obstacles, sv_hull_info* info);
 /* ms of the last sv_batch_road_hull from HIP events on the batch stream. Synchronises the batch stream. */
 int sv_batch_road_hull_ms(sv_batch* b, float* ms);
+/* The result image (sv_result_image) of every frame, on the device: one kernel that reads the batch's BGR (the
+ * image the pipeline read its colours from; left unchanged) and the obstacle stage's bitmaps, vertices and infos,
+ * and writes a buffer of its own (frames x H x W x 3 bytes, allocated by the first call). SV_E_STATE without a
+ * current obstacle stage (sv_batch_road_hull after the last clean-up) or on a batch created without BGR; whatever
+ * invalidates the obstacle stage invalidates the result. For a batch of cropped frames (sv_batch_pair_shape) the
+ * result covers the batch's H x W, like sv_batch_road_map. H, W <= 4096. */
+int sv_batch_result(sv_batch* b, int sync);
+/* One frame's result image, H x W x 3 u8. */
+int sv_batch_read_result(sv_batch* b, int frame, uint8_t* out);
+/* ms of the last sv_batch_result from HIP events on the batch stream. Synchronises the batch stream. */
+int sv_batch_result_ms(sv_batch* b, float* ms);
 
 /* Batched RANSAC (stereovision.py:84-94 for every frame):
  * maskpoints = the fp64 step-2 projection of the batch's disparity under the
@@ -504,7 +547,8 @@ typedef struct {
     int road;            /* 0 none, 1 road raster + walk, 2 + imageRoadMap, 3 road raster + walk + the
                             clean-up (sv_batch_road_clean; its mask: sv_loop_road_mask), 4 all of 3 + the
                             obstacle stage (sv_batch_road_hull; results: sv_batch_read_road_hull of the
-                            batch sv_loop_batch returns), inside the timeline's "road" stage           */
+                            batch sv_loop_batch returns), 5 all of 4 + the result image
+                            (sv_batch_result; sv_batch_read_result), inside the timeline's "road" stage */
 } sv_loop_params;
 typedef struct sv_loop sv_loop;
 /* carmask: the grey H x W mask of maskDisparity (functions.py:35, :169-172), NULL for none. */

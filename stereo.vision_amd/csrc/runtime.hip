@@ -19,6 +19,8 @@
 #include "svx_hull.h"
 #include "svx_hull_host.h"
 #include "svx_morph.h"
+#include "svx_result.h"
+#include "svx_result_host.h"
 #include "svx_sgbm.h"
 
 using namespace svx;
@@ -153,6 +155,7 @@ struct Device {
     DevBuf disp, bgr, xyz, rgb, ctrl, xy, aux, aux2;
     DevBuf mbits;                     // sv_sanitise_road: the image, the cleaned image and the mask as bitmaps
     DevBuf hull;                      // sv_road_obstacles: bitmaps, vertices and info (HullLayout)
+    DevBuf res;                       // sv_result_image: image, obstacle bitmap, vertices and info (ResultLayout)
     DevBuf sg_l, sg_r, sg_out, sg_filt, sg_hist;   // host-frame SGBM / grey drop-ins
     SgbmBufs sg;
     Tables tables;
@@ -309,6 +312,10 @@ struct sv_batch {
     const FramePlane* hull_planes = nullptr;
     int hull_plane_stride = 0;
     HullPlane hull_shared{};
+    // the result image (sv_batch_result): frames x H rows of 3 W bytes, the BGR's layout; made on first use
+    DevBuf rimg;
+    bool result_fresh = false;  // rimg holds the result of the current obstacle stage (reset with hull_fresh)
+    hipEvent_t rev[2] = {nullptr, nullptr};
     DevBuf mpts, rres;          // one frame's maskpoints as fp64 (read-back scratch); counts + batched RANSAC results
     DevBuf prev0buf, rdbuf;     // the host prev0 of sv_batch_prepass; sv_batch_read_disp's masked frame (batch-owned:
                                 // the device-wide drop-in scratch is used on other streams)
@@ -653,7 +660,7 @@ int sv_batch_destroy(sv_batch* b) {
                       &b->carmask, &b->road, &b->rmap, &b->nz, &b->nzcount, &b->mpts, &b->mpk, &b->rres, &b->rtab, &b->rtrace, &b->fplanes, &b->dplane, &b->abc,
                       &b->pairL, &b->pairR, &b->rsidx, &b->rtri, &b->bgrL, &b->bgrR,
                       &b->glut, &b->ghist, &b->sgflags, &b->prev0buf, &b->rdbuf, &b->rbits, &b->roff, &b->raw, &b->rmask, &b->cpack,
-                      &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff, &b->hbuf})
+                      &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff, &b->hbuf, &b->rimg})
         if (x->p) (void)hipFree(x->p);
     if (b->hcnt) (void)hipHostFree(b->hcnt);
     if (b->cnt_ev) (void)hipEventDestroy(b->cnt_ev);
@@ -663,6 +670,8 @@ int sv_batch_destroy(sv_batch* b) {
     for (auto& ev : b->cev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->hev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : b->rev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->pool) (void)hipEventDestroy(ev);
     for (auto& ev : b->sync_ev) (void)hipEventDestroy(ev);
@@ -1672,7 +1681,7 @@ int sv_batch_road_clean(sv_batch* b, int sync) {
     const size_t px = (size_t)H * b->W, words = (size_t)H * WW;
     for (hipEvent_t& e : b->cev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    b->clean_fresh = b->hull_fresh = false;
+    b->clean_fresh = b->hull_fresh = b->result_fresh = false;
     b->ccap = ((size_t)H * Wu + 63) / 64 * 64;
     HIP_TRY(b->cbits.ensure(sizeof(uint32_t) * words * b->frames));
     HIP_TRY(b->cimg.ensure(px * b->frames));
@@ -1830,7 +1839,7 @@ int sv_batch_road_hull(sv_batch* b, int sync) {
     hipStream_t s = b->stream;
     for (hipEvent_t& e : b->hev)
         if (!e) HIP_TRY(hipEventCreate(&e));
-    b->hull_fresh = false;
+    b->hull_fresh = b->result_fresh = false;
     const HullLayout l = hull_layout(b->H, b->Wu, b->frames, false);
     HIP_TRY(b->hbuf.ensure(l.bytes));
     char* base = b->hbuf.as<char>();
@@ -1887,6 +1896,103 @@ int sv_batch_read_road_hull(sv_batch* b, int frame, int32_t* hull_pts, int64_t c
             HIP_TRY(hipMemcpy(hull_pts, reinterpret_cast<const int32_t*>(base + l.off_pts) + 4 * (size_t)b->H * frame,
                               sizeof(int32_t) * 2 * (size_t)hi.n, hipMemcpyDeviceToHost));
     }
+    return SV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the result image (stereovision.py:181-209, functions.py:390-394, :424-431): kernels/result.hip
+// ---------------------------------------------------------------------------
+static_assert(kResultHostMaxH == kResultMaxH && kResultHostMaxW == kResultMaxW &&
+                  kResultHostMaxCoord == kResultMaxCoord && kResultHostMaxVerts == kResultMaxVerts,
+              "svx_result_host.h and svx_result.h disagree");
+
+int sv_result_image(const uint8_t* bgr, const uint8_t* obstacles, const int32_t* hull_pts, int64_t n,
+                    const sv_hull_info* info, int H, int W, uint8_t* out) {
+    if (const char* why = result_check_args(bgr, obstacles, hull_pts, n, info, H, W, out))
+        return fail(SV_E_ARG, "sv_result_image: bad arguments (%s)", why);
+    int dev;
+    if (int rc = current_device(&dev)) return rc;
+    Device* d;
+    if (int rc = dev_get(dev, &d)) return rc;
+    std::lock_guard<std::mutex> lk(d->mu);
+    hipStream_t s = d->stream;
+    const ResultLayout l = result_layout(H, W, n);
+    HIP_TRY(d->res.ensure(l.bytes));
+    HIP_TRY(d->bgr.ensure(l.img));
+    char* base = d->res.as<char>();
+    uint32_t* bits = reinterpret_cast<uint32_t*>(base + l.off_bits);
+    int32_t* dpts = reinterpret_cast<int32_t*>(base + l.off_pts);
+    sv_hull_info* dinfo = reinterpret_cast<sv_hull_info*>(base + l.off_info);
+    sv_hull_info hi = info ? *info : sv_hull_info{0, 0, 0, 0, 0, 0};
+    hi.n = (int32_t)n;
+    // the BGR at the batch's stride (pad columns zero), the obstacles as a bitmap
+    if (l.pitch != W) HIP_TRY(hipMemsetAsync(d->bgr.p, 0, l.img, s));
+    HIP_TRY(hipMemcpy2DAsync(d->bgr.p, l.ld3, bgr, 3 * (size_t)W, 3 * (size_t)W, H, hipMemcpyHostToDevice, s));
+    if (int rc = upload_u8(d->aux, obstacles, H, W, l.pitch, s)) return rc;
+    HIP_TRY(launch_morph_pack(d->aux.as<uint8_t>(), (int64_t)H * l.pitch, l.pitch, W, H, 1, bits, s));
+    if (n > 0) HIP_TRY(hipMemcpyAsync(dpts, hull_pts, sizeof(int32_t) * 2 * (size_t)n, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dinfo, &hi, sizeof hi, hipMemcpyHostToDevice, s));
+    HIP_TRY(launch_result(d->bgr.as<uint8_t>(), (int64_t)l.img, l.ld3, bits, dpts, 0, dinfo, 1, H, W,
+                          reinterpret_cast<uint8_t*>(base + l.off_out), s));
+    HIP_TRY(hipMemcpy2DAsync(out, 3 * (size_t)W, base + l.off_out, l.ld3, 3 * (size_t)W, H, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SV_OK;
+}
+
+int sv_batch_result(sv_batch* b, int sync) {
+    if (!b) return fail(SV_E_ARG, "null batch");
+    if (!b->with_bgr) return fail(SV_E_STATE, "the result image needs the batch's BGR (with_bgr)");
+    if (!b->clean_fresh || !b->hull_fresh)
+        return fail(SV_E_STATE, "no current obstacle stage (sv_batch_road_hull first)");
+    if (b->H > kResultMaxH || b->Wu > kResultMaxW)
+        return fail(SV_E_ARG, "the result image takes frames of at most 4096 x 4096");
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    for (hipEvent_t& e : b->rev)
+        if (!e) HIP_TRY(hipEventCreate(&e));
+    b->result_fresh = false;
+    const size_t px3 = (size_t)b->H * b->W * 3;
+    HIP_TRY(b->rimg.ensure(px3 * b->frames, false, 0, true));   // a buffer of its own: the pipeline reads the BGR
+    const HullLayout l = hull_layout(b->H, b->Wu, b->frames, false);
+    const char* base = b->hbuf.as<char>();
+    HIP_TRY(hipEventRecord(b->rev[0], s));
+    // probe (tools/_probe_result.py; the picture is NOT made): the floor of this traffic, a device copy of the BGR
+    // into the result buffer between the same events
+    const char* copy_only = svx_knob("SVX_RESULT_COPY");
+    if (copy_only && *copy_only == '1') {
+        HIP_TRY(hipMemcpyAsync(b->rimg.p, b->bgr.p, px3 * b->frames, hipMemcpyDeviceToDevice, s));
+    } else {
+        HIP_TRY(launch_result(b->bgr.as<uint8_t>(), (int64_t)px3, 3 * b->W,
+                              reinterpret_cast<const uint32_t*>(base + l.off_obst),
+                              reinterpret_cast<const int32_t*>(base + l.off_pts), 4 * (int64_t)b->H,
+                              reinterpret_cast<const sv_hull_info*>(base + l.off_info), b->frames, b->H, b->Wu,
+                              b->rimg.as<uint8_t>(), s));
+    }
+    HIP_TRY(hipEventRecord(b->rev[1], s));
+    b->result_fresh = true;
+    if (sync) HIP_TRY(hipStreamSynchronize(s));
+    return SV_OK;
+}
+
+int sv_batch_result_ms(sv_batch* b, float* ms) {
+    if (!b || !ms) return fail(SV_E_ARG, "null batch or ms");
+    if (!b->clean_fresh || !b->hull_fresh || !b->result_fresh)
+        return fail(SV_E_STATE, "no result image (sv_batch_result first)");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipEventSynchronize(b->rev[1]));
+    HIP_TRY(hipEventElapsedTime(ms, b->rev[0], b->rev[1]));
+    return SV_OK;
+}
+
+int sv_batch_read_result(sv_batch* b, int frame, uint8_t* out) {
+    if (!b || !out || frame < 0 || frame >= b->frames) return fail(SV_E_ARG, "bad args");
+    if (!b->clean_fresh || !b->hull_fresh || !b->result_fresh)
+        return fail(SV_E_STATE, "no result image (sv_batch_result first)");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    const size_t px3 = (size_t)b->H * b->W * 3;
+    HIP_TRY(hipMemcpy2D(out, (size_t)b->Wu * 3, b->rimg.as<uint8_t>() + px3 * frame, (size_t)b->W * 3,
+                        (size_t)b->Wu * 3, b->H, hipMemcpyDeviceToHost));
     return SV_OK;
 }
 
@@ -2802,9 +2908,9 @@ int sv_loop_create(int device, const sv_loop_params* prm, const sv_camera* cam, 
     *out = nullptr;
     const sv_loop_params& q = *prm;
     if (q.frames < 1 || q.slots < 1 || q.slots > 8 || (q.source != 0 && q.source != 1) || q.prepass < 0 ||
-        q.prepass > 2 || q.road < 0 || q.road > 4 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
+        q.prepass > 2 || q.road < 0 || q.road > 5 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
         return fail(SV_E_ARG, "sv_loop_create: bad parameters (frames >= 1, 1 <= slots <= 8, source 0/1, prepass "
-                              "0..2, road 0..4, step 1/2, trials >= 0, k >= 1)");
+                              "0..2, road 0..5, step 1/2, trials >= 0, k >= 1)");
     // what a submit would only find out after enqueueing the input and pre-pass stages (the RANSAC and synthetic
     // input limits of batch_ransac_prepare / sv_batch_synth)
     if (q.trials > 4096 || q.k > 1024) return fail(SV_E_ARG, "sv_loop_create: RANSAC trials <= 4096, k <= 1024");
@@ -2933,8 +3039,11 @@ static int loop_enqueue_tail(sv_loop* L, int64_t seq, uint64_t gate_epoch) {
     if (q.road >= 3) {   // sanitiseRoadImage's clean-up of the images just made (functions.py:346-366)
         if (int rc = sv_batch_road_clean(b, 0)) return rc;
     }
-    if (q.road == 4) {   // the obstacle stage on the cleaned images (stereovision.py:170-189)
+    if (q.road >= 4) {   // the obstacle stage on the cleaned images (stereovision.py:170-189)
         if (int rc = sv_batch_road_hull(b, 0)) return rc;
+    }
+    if (q.road == 5) {   // the result image from the BGR and the obstacle stage (stereovision.py:181-209)
+        if (int rc = sv_batch_result(b, 0)) return rc;
     }
     HIP_TRY(end(kLsRoad));
     if (L->pending == seq) L->pending = -1;

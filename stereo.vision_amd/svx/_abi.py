@@ -72,6 +72,7 @@ SIGNATURES = {
     "sv_road_obstacles": [P, P, ctypes.POINTER(Plane), I, I, ctypes.POINTER(Camera), P, I64, P, P,
                           ctypes.POINTER(HullInfo)],
     "sv_min_circle_centre": [P, I64, P],
+    "sv_result_image": [P, P, P, I64, ctypes.POINTER(HullInfo), I, I, P],
     "sv_batch_road_raster": [P, I],
     "sv_batch_nonzero": [P, I],
     "sv_batch_read_road": [P, I, P, P, I64, PI64],
@@ -85,6 +86,9 @@ SIGNATURES = {
     "sv_batch_road_hull": [P, I],
     "sv_batch_read_road_hull": [P, I, P, I64, P, P, ctypes.POINTER(HullInfo)],
     "sv_batch_road_hull_ms": [P, PF],
+    "sv_batch_result": [P, I],
+    "sv_batch_read_result": [P, I, P],
+    "sv_batch_result_ms": [P, PF],
     "sv_point_errors": [P, I64, I64, P, P],
     "sv_hue_histogram": [P, I64, I64, P, P, P],
     "sv_select_less": [P, I64, D, P, PI64],

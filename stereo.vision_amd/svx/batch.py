@@ -312,6 +312,23 @@ class Batch:
         return _abi.hull_result(self.H, self.W, images, lambda pts, cap, m, o, info: _abi.call(
             "sv_batch_read_road_hull", self._h, frame, _abi.ptr(pts), cap, _abi.ptr(m), _abi.ptr(o), info))
 
+    def result(self, sync=True):
+        """The result image (stereovision.py:181-209) of every frame, on the device: the batch's BGR dimmed, the
+        obstacles tinted, the hull outlined and the glyph drawn; after road_hull(), on a batch with BGR."""
+        _abi.call("sv_batch_result", self._h, int(sync))
+
+    def result_ms(self):
+        """ms of the last result(), from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_result_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
+    def read_result(self, frame):
+        """One frame's result image, (H, W, 3) uint8 BGR."""
+        out = np.empty((self.H, self.W, 3), np.uint8)
+        _abi.call("sv_batch_read_result", self._h, frame, _abi.ptr(out))
+        return out
+
     def ransac(self, seed_base, trials, k=600, first_frame=0, camera=None, sync=True):
         """RANSAC(maskpoints, trials) of every frame on the device (stereovision.py:84-94), frame F
         drawing what CPython draws after random.seed(seed_base + first_frame + F)."""

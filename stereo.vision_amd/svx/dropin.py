@@ -38,7 +38,8 @@ reference:
   walk; returns ``(img, np.matrix(pts))``. Installed only with ``install(.., morphology=True)``.
 * ``getCenterPoint(points)`` (functions.py:418-421): the centre of the exact minimum enclosing
   circle; installed only with ``install(.., hull=True)``. ``road_obstacles`` gives the whole
-  obstacle stage (hull, hull mask, obstacles, centre, glyph tip) of a cleaned road image.
+  obstacle stage (hull, hull mask, obstacles, centre, glyph tip) of a cleaned road image,
+  ``result_image`` the picture drawn from it (stereovision.py:181-209; array form only).
 * disparity pre-pass (functions.py:141-172): ``fillDisparity`` (new array, or
   the input itself when there is no previous frame), ``fillAltDisparity`` (in
   place, returns its argument), ``maskDisparity`` (new array; the mask is the
@@ -314,6 +315,40 @@ def road_obstacles(cleaned, disparity=None, abc=None, camera=None):
     return _abi.hull_result(H, W, True, lambda pts, cap, m, o, info: _abi.call(
         "sv_road_obstacles", _abi.ptr(im), _abi.ptr(dp), pl, H, W, ctypes.byref(cam), _abi.ptr(pts), cap,
         _abi.ptr(m), _abi.ptr(o), info))
+
+
+def result_image(imgL, obstacles, hull, centre=None, tip=None):  # noqa: N803
+    """The "Result" image of stereovision.py:181-209 on the GPU: imgL (H, W, 3) uint8 BGR dimmed to 0.6 with the
+    obstacles (H, W, non-zero = obstacle) tinted yellow (cv2.addWeighted), the hull outlined in red (drawRoadLine)
+    and, with a centre and a tip, the road-normal glyph (drawNormalLine). It takes what road_obstacles returns:
+    result_image(imgL, r["obstacles"], r["hull"], r["centre"], r["tip"]). hull: (n, 1, 2) or (n, 2) integers, a
+    convex polygon in outline order; no vertex: imgL unchanged. The overlay is cv2's byte for byte; the strokes are
+    the exact capsules and disc of include/svx.h (sv_result_image), unpinned against cv2's rasteriser."""
+    im = np.ascontiguousarray(_as_u8(imgL, 3, "image"))
+    if im.shape[2] != 3:
+        raise ValueError(f"image shape {im.shape}: (H, W, 3) expected")
+    H, W = im.shape[:2]
+    ob = np.ascontiguousarray(_as_u8(obstacles, 2, "obstacles"))
+    if ob.shape != (H, W):
+        raise ValueError(f"obstacles shape {ob.shape} != image shape {(H, W)}")
+    hp = np.asarray(hull)
+    if hp.size and (hp.dtype.kind not in "iu" or hp.size % 2):
+        raise TypeError("hull: an (n, 1, 2) or (n, 2) integer array")
+    hp = hp.reshape(-1, 2).astype(np.int64)
+    if hp.size and np.abs(hp).max() > 16383:
+        raise ValueError("hull: coordinates beyond +-16383")
+    hp = np.ascontiguousarray(hp, np.int32)
+    info = _abi.HullInfo()
+    if centre is not None:
+        info.cx, info.cy, info.valid = int(centre[0]), int(centre[1]), 1
+        if tip is not None:
+            tx, ty = int(tip[0]), int(tip[1])
+            if abs(tx) < 2 ** 63 and abs(ty) < 2 ** 63:   # beyond int64 the reference's int() result cannot be drawn
+                info.tipx, info.tipy, info.valid = tx, ty, 3
+    out = np.empty((H, W, 3), np.uint8)
+    _abi.call("sv_result_image", _abi.ptr(im), _abi.ptr(ob), _abi.ptr(hp) if len(hp) else None, len(hp),
+              ctypes.byref(info), H, W, _abi.ptr(out))
+    return out
 
 
 def getCenterPoint(points):  # noqa: N802

@@ -11,7 +11,8 @@ in batches and every batch runs the non-cv2 stages of that function:
           -> road raster + non-zero walk (+ imageRoadMap)               stereovision.py:131-156
              (road="clean": + sanitiseRoadImage's clean-up and its walk, functions.py:346-366;
               Batch.read_road_clean; road="obstacles": + the obstacle stage, stereovision.py:170-189;
-              Batch.read_road_hull)
+              Batch.read_road_hull; road="result": + the result image, stereovision.py:181-209;
+              Batch.read_result)
 
 FrameLoop keeps `slots` batches in flight, one HIP stream each; a stage of batch k waits for the same stage of
 batch k - 1 (a device event), and the RANSAC evaluation of batch k for batch k - 1's road pass, so with two slots
@@ -38,7 +39,7 @@ from .batch import CAMERA, Batch
 STAGES = ("input", "prepass", "maskpoints", "draw", "eval", "pipeline", "road")
 _SOURCES = {"caller": 0, "synth": 1}
 _PREPASS = {"none": 0, "previous": 1, "mean": 2}
-_ROAD = {"none": 0, "walk": 1, "map": 2, "clean": 3, "obstacles": 4}
+_ROAD = {"none": 0, "walk": 1, "map": 2, "clean": 3, "obstacles": 4, "result": 5}
 
 
 class FrameLoop:
@@ -67,8 +68,8 @@ class FrameLoop:
                 raise
 
     def road_mask(self, mask):
-        """The road_threshold_mask of road="clean" / "obstacles" (H x W uint8, non-zero keeps a pixel; None: all
-        ones), for the batches whose road stage is enqueued from now on (sv_loop_road_mask)."""
+        """The road_threshold_mask of road="clean" / "obstacles" / "result" (H x W uint8, non-zero keeps a pixel;
+        None: all ones), for the batches whose road stage is enqueued from now on (sv_loop_road_mask)."""
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         if m is not None and m.shape != (self.H, self.W):
             raise ValueError(f"road_mask shape {m.shape} != {(self.H, self.W)}")
