@@ -16,11 +16,9 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include <cstdio>
 #include <cstring>
-#include <string>
 
-#include "../../include/svx.h"
+#include "svx_runtime.h"
 
 static_assert(sizeof(ncclUniqueId) == SV_UNIQUE_ID_BYTES, "unique id size");
 
@@ -30,10 +28,6 @@ struct sv_comm {
     hipStream_t stream = nullptr;
     void* buf = nullptr;  // 4 KB device scratch of the synchronous host-plane / count calls (on c->stream)
 };
-
-extern "C" int sv_comm_set_error(const char* msg);                                  // runtime.hip
-extern "C" int sv_batch_stream_internal(sv_batch* b, int* device, hipStream_t* stream,
-                                        double** abc_slot);   // runtime.hip
 
 namespace {
 // The root's host plane into the comm's device buffer, on the batch stream.
@@ -46,32 +40,22 @@ __global__ void store_abc_kernel(double a, double b, double c, double* __restric
 }
 }  // namespace
 
-#define NCCL_TRY(expr)                                                              \
-    do {                                                                            \
-        ncclResult_t r_ = (expr);                                                   \
-        if (r_ != ncclSuccess) {                                                    \
-            char m_[256];                                                           \
-            snprintf(m_, sizeof m_, "%s: %s", #expr, ncclGetErrorString(r_));       \
-            sv_comm_set_error(m_);                                                  \
-            return SV_E_COMM;                                                       \
-        }                                                                           \
+#define NCCL_TRY(expr)                                                                             \
+    do {                                                                                           \
+        ncclResult_t r_ = (expr);                                                                  \
+        if (r_ != ncclSuccess) return fail(SV_E_COMM, "%s: %s", #expr, ncclGetErrorString(r_));    \
     } while (0)
 
-#define HIPC_TRY(expr)                                                              \
-    do {                                                                            \
-        hipError_t e_ = (expr);                                                     \
-        if (e_ != hipSuccess) {                                                     \
-            char m_[256];                                                           \
-            snprintf(m_, sizeof m_, "%s: %s", #expr, hipGetErrorString(e_));        \
-            sv_comm_set_error(m_);                                                  \
-            return SV_E_HIP;                                                        \
-        }                                                                           \
+#define HIPC_TRY(expr)                                                                             \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess) return fail(SV_E_HIP, "%s: %s", #expr, hipGetErrorString(e_));       \
     } while (0)
 
 extern "C" {
 
 int sv_comm_unique_id(uint8_t* out_id) {
-    if (!out_id) return sv_comm_set_error("null id"), SV_E_ARG;
+    if (!out_id) return fail(SV_E_ARG, "null id");
     ncclUniqueId id;
     NCCL_TRY(ncclGetUniqueId(&id));
     std::memcpy(out_id, &id, sizeof id);
@@ -80,7 +64,7 @@ int sv_comm_unique_id(uint8_t* out_id) {
 
 int sv_comm_init(int nranks, int rank, const uint8_t* id, int device, sv_comm** out) {
     if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks)
-        return sv_comm_set_error("sv_comm_init: bad arguments"), SV_E_ARG;
+        return fail(SV_E_ARG, "sv_comm_init: bad arguments");
     *out = nullptr;
     HIPC_TRY(hipSetDevice(device));
     sv_comm* c = new sv_comm;
@@ -114,7 +98,7 @@ int sv_comm_destroy(sv_comm* c) {
 }
 
 int sv_comm_broadcast_plane(sv_comm* c, sv_plane* inout, int root) {
-    if (!c || !inout) return sv_comm_set_error("null"), SV_E_ARG;
+    if (!c || !inout) return fail(SV_E_ARG, "null");
     HIPC_TRY(hipSetDevice(c->device));
     double h[3] = {inout->a, inout->b, inout->c};
     HIPC_TRY(hipMemcpyAsync(c->buf, h, sizeof h, hipMemcpyHostToDevice, c->stream));
@@ -128,7 +112,7 @@ int sv_comm_broadcast_plane(sv_comm* c, sv_plane* inout, int root) {
 }
 
 int sv_comm_init_all(int n, const int* devices, sv_comm** out) {
-    if (n < 1 || n > 64 || !devices || !out) return sv_comm_set_error("sv_comm_init_all: bad arguments"), SV_E_ARG;
+    if (n < 1 || n > 64 || !devices || !out) return fail(SV_E_ARG, "sv_comm_init_all: bad arguments");
     ncclComm_t comms[64];
     for (int i = 0; i < n; ++i) out[i] = nullptr;
     NCCL_TRY(ncclCommInitAll(comms, n, devices));
@@ -163,19 +147,22 @@ int sv_comm_group_end(void) {
 }
 
 int sv_comm_broadcast_plane_dev(sv_comm* c, sv_batch* b, const sv_plane* plane, int root, const double** out_dplane) {
-    if (!c || !b || !out_dplane) return sv_comm_set_error("sv_comm_broadcast_plane_dev: null"), SV_E_ARG;
-    int dev = -1;
-    hipStream_t s = nullptr;
-    if (sv_batch_stream_internal(b, &dev, &s, nullptr) != SV_OK || dev != c->device)
-        return sv_comm_set_error("sv_comm_broadcast_plane_dev: batch and comm are on different devices"), SV_E_ARG;
+    if (!c || !b || !out_dplane) return fail(SV_E_ARG, "sv_comm_broadcast_plane_dev: null");
+    if (b->device != c->device)
+        return fail(SV_E_ARG, "sv_comm_broadcast_plane_dev: batch and comm are on different devices");
     int rank = -1;
     NCCL_TRY(ncclCommUserRank(c->comm, &rank));
-    if (rank == root && !plane) return sv_comm_set_error("sv_comm_broadcast_plane_dev: the root needs the plane"), SV_E_ARG;
+    if (rank == root && !plane) return fail(SV_E_ARG, "sv_comm_broadcast_plane_dev: the root needs the plane");
     HIPC_TRY(hipSetDevice(c->device));
-    // the plane lands in the batch's own slot, written and read on the batch's stream only
-    double* buf = nullptr;
-    if (sv_batch_stream_internal(b, &dev, &s, &buf) != SV_OK)
-        return sv_comm_set_error("sv_comm_broadcast_plane_dev: no device memory for the plane slot"), SV_E_HIP;
+    // the plane (3 doubles) lands in the batch's own slot, written and read on the batch's stream only (collectives
+    // are ordered on it), so that two batches — or a comm's other calls — never share the buffer a pending pipeline
+    // reads the plane from
+    hipStream_t s = b->stream;
+    if (b->abc.ensure(sizeof(double) * 3) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(SV_E_HIP, "sv_comm_broadcast_plane_dev: no device memory for the plane slot");
+    }
+    double* buf = b->abc.as<double>();
     if (rank == root) {
         hipLaunchKernelGGL(store_abc_kernel, dim3(1), dim3(64), 0, s, plane->a, plane->b, plane->c, buf);
         HIPC_TRY(hipGetLastError());
@@ -188,9 +175,9 @@ int sv_comm_broadcast_plane_dev(sv_comm* c, sv_batch* b, const sv_plane* plane, 
 int sv_multi_pipeline(int n, sv_comm* const* comms, sv_batch* const* batches, const sv_camera* cam,
                       const sv_plane* plane, int root, double point_thr, int hist_thr, int sync) {
     if (n < 1 || !comms || !batches || !cam || !plane || root < 0 || root >= n)
-        return sv_comm_set_error("sv_multi_pipeline: bad arguments"), SV_E_ARG;
+        return fail(SV_E_ARG, "sv_multi_pipeline: bad arguments");
     const double* dplane[64];
-    if (n > 64) return sv_comm_set_error("sv_multi_pipeline: at most 64 devices"), SV_E_ARG;
+    if (n > 64) return fail(SV_E_ARG, "sv_multi_pipeline: at most 64 devices");
     NCCL_TRY(ncclGroupStart());
     for (int i = 0; i < n; ++i) {
         const int rc = sv_comm_broadcast_plane_dev(comms[i], batches[i], i == root ? plane : nullptr, root, &dplane[i]);
@@ -209,7 +196,7 @@ int sv_multi_pipeline(int n, sv_comm* const* comms, sv_batch* const* batches, co
 }
 
 int sv_comm_allreduce_i64(sv_comm* c, int64_t* inout, int n) {
-    if (!c || !inout || n < 0 || n > 512) return sv_comm_set_error("bad args"), SV_E_ARG;
+    if (!c || !inout || n < 0 || n > 512) return fail(SV_E_ARG, "bad args");
     if (n == 0) return SV_OK;
     HIPC_TRY(hipSetDevice(c->device));
     HIPC_TRY(hipMemcpyAsync(c->buf, inout, 8 * (size_t)n, hipMemcpyHostToDevice, c->stream));

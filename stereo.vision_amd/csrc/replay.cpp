@@ -1,5 +1,5 @@
 // Host replay of CPython's random draws for the RANSAC drop-in (functions.py:240-298), SURVEY §8f rank 1:
-// sv_ransac_draw and the draw side of sv_ransac (runtime.hip). Plain C++ for the host compiler; the trial
+// sv_ransac_draw and the draw side of sv_ransac (rt_ransac.hip). Plain C++ for the host compiler; the trial
 // evaluation kernels are kernels/ransac.hip.
 //
 // The reference draws from Python's global `random` (unseeded). To be a drop-in whose effect on the program is

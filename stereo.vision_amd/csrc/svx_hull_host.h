@@ -1,4 +1,4 @@
-// Host-only part of the obstacle stage's runtime (runtime.hip): the argument checks of sv_road_obstacles and the
+// Host-only part of the obstacle stage's runtime (rt_road.hip): the argument checks of sv_road_obstacles and the
 // layout of the device buffer that holds a call's bitmaps, vertices and results. No HIP in here, so that
 // tools/hull_host_check.cpp can run it under the host sanitizers without a device (by hand, on the development
 // machine only).
@@ -10,7 +10,7 @@
 
 namespace svx {
 
-constexpr int kHullHostMaxH = 4096;   // = kHullMaxH (svx_hull.h; runtime.hip asserts it)
+constexpr int kHullHostMaxH = 4096;   // = kHullMaxH (svx_hull.h; rt_road.hip asserts it)
 
 // nullptr when sv_road_obstacles' arguments are in range, else what is wrong with them
 inline const char* hull_check_args(const void* cleaned, const void* cam, int H, int W, const void* hull_pts,

@@ -1,4 +1,4 @@
-// Host-only part of the result image's runtime (runtime.hip): the argument checks of sv_result_image and the layout
+// Host-only part of the result image's runtime (rt_road.hip): the argument checks of sv_result_image and the layout
 // of the device buffer that holds a call's image, obstacle bitmap, vertices and info. No HIP in here, so that
 // tools/result_host_check.cpp can run it under the host sanitizers without a device (by hand, on the development
 // machine only).
@@ -11,7 +11,7 @@
 namespace svx {
 
 constexpr int kResultHostMaxH = 4096, kResultHostMaxW = 4096;   // = kResultMaxH, kResultMaxW (svx_result.h;
-constexpr int kResultHostMaxCoord = 16383;                      //   runtime.hip asserts them)
+constexpr int kResultHostMaxCoord = 16383;                      //   rt_road.hip asserts them)
 constexpr int kResultHostMaxVerts = 8192;
 
 // how often the sign of the non-zero values of d(0) .. d(n - 1) changes around the ring

@@ -2,7 +2,8 @@
 
 Layers (bottom-up):
   K    hand-written gfx950 HIP kernels        csrc/kernels/*.hip
-  R    C++ runtime (device, streams, buffers) csrc/runtime.hip, csrc/comm.hip (RCCL)
+  R    C++ runtime (device, streams, buffers) csrc/svx_runtime.h, csrc/runtime.hip, one csrc/rt_*.hip a stage
+                                              (DESIGN §8.3), csrc/comm.hip (RCCL)
   ABI  extern "C" libsvx.so                   include/svx.h
   P    ctypes binding + drop-in + batch API   svx/_abi.py, svx/dropin.py, svx/batch.py
        multi-GPU driver (one process per GPU) svx/dist.py

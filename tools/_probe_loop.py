@@ -19,7 +19,8 @@ ONLY = os.environ.get("PROBE_ONLY")   # e.g. "caller2": that configuration alone
 for source, slots in (("caller", 2), ("caller", 1), ("synth", 2), ("caller", 3), ("synth", 3)):
     if ONLY and f"{source}{slots}" not in ONLY.split(","):
         continue
-    with FrameLoop(F, slots=slots, source=source, carmask=mask) as loop:
+    # PROBE_ROAD: how far the road chain goes ("walk", the default, ... "result")
+    with FrameLoop(F, slots=slots, source=source, carmask=mask, road=os.environ.get("PROBE_ROAD", "walk")) as loop:
         NB = int(os.environ.get("PROBE_BATCHES", 6))   # batches submitted: 2 warm-up, NB - 2 timed
         for i in range(NB):
             if i == 2:
