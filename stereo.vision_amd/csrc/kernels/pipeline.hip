@@ -170,8 +170,8 @@ __device__ __forceinline__ void hist_tile(const PipeBuffers& bf, int frame, int 
             nv += (in[i].d[k] != 0 && gx < p.Wg) ? 1u : 0u;
             if (live && point_keep1<STEP>(in[i].d[k], gx, y, yc, p)) {
                 keep |= 1u << (4 * i + k);
-                const int bin = (p.ablate & 1) ? 0 : point_bin<STEP>(in[i], k);
-                if (!(p.ablate & 2)) atomicAdd(&sh.hist[bin], 1u);
+                const int bin = ablated(p.ablate, 1) ? 0 : point_bin<STEP>(in[i], k);
+                if (!ablated(p.ablate, 2)) atomicAdd(&sh.hist[bin], 1u);
             }
         }
     }
@@ -456,7 +456,7 @@ __global__ __launch_bounds__(256) void stage_kernel(PipeBuffers bf, int p2_frame
     const int b = blockIdx.x;
     const int both = 2 * min(n1, n2);
     int role, idx;   // role 2 = pass 2, 1 = pass 1
-    if (p.ablate & 64) {   // diagnostic: no interleave (all pass-2 blocks first)
+    if (ablated(p.ablate, 64)) {   // diagnostic: no interleave (all pass-2 blocks first)
         role = b < n2 ? 2 : 1;
         idx = b < n2 ? b : b - n2;
     } else if (b < both) {
@@ -468,9 +468,9 @@ __global__ __launch_bounds__(256) void stage_kernel(PipeBuffers bf, int p2_frame
     }
     const int fl = idx / tiles, t = idx - fl * tiles;
     if (role == 2) {
-        if (!(p.ablate & 256)) compact_tile<STEP>(bf, p2_frame0 + fl, t, tiles, p, sh.p2);
+        if (!ablated(p.ablate, 256)) compact_tile<STEP>(bf, p2_frame0 + fl, t, tiles, p, sh.p2);
     } else {
-        if (!(p.ablate & 128)) hist_tile<STEP, PF>(bf, p1_frame0 + fl, t, tiles, p, sh.p1);
+        if (!ablated(p.ablate, 128)) hist_tile<STEP, PF>(bf, p1_frame0 + fl, t, tiles, p, sh.p1);
     }
 }
 

@@ -229,7 +229,6 @@ struct RansacShared {
     uint32_t* pool_list;                      // pool branch: the virtual pool's entries (same words, <= k)
     int k;
     uint32_t spread;                          // (a power of two, <= the bitmap's words) - 1: rejected claims' words
-    int ablate;                               // DIAGNOSTIC (SVX_RANSAC_ABLATE, diag build)
 };
 
 // CPython's init_genrand + init_by_array (Modules/_randommodule.c) for a
@@ -676,7 +675,6 @@ __global__ __launch_bounds__(64 * WPG) void ransac_draw_kernel(const uint32_t* _
     sh.pool_list = rb_dyn;
     sh.k = k;
     sh.spread = bitmap_words >= 64 ? 63u : bitmap_words >= 32 ? 31u : bitmap_words >= 16 ? 15u : bitmap_words >= 8 ? 7u : 3u;
-    sh.ablate = ablate;
     const int lane = lane_id();
     // one frame a wave, or (the frame loop, gridDim.x < nframes) a wave's frames one after the other: fewer
     // waves resident at once hold less LDS beside the other batch's pipeline
@@ -690,11 +688,10 @@ __global__ __launch_bounds__(64 * WPG) void ransac_draw_kernel(const uint32_t* _
         }
         continue;
     }
-#ifdef SVX_DIAG
     // DIAGNOSTIC (diagnostic build, SVX_RANSAC_ABLATE bit 128; results invalid): the wave holds its resources for
     // 4 ms of wall clock and draws nothing (the evaluation then reads stale indices, clamped) — does the pipeline
     // beside the draw slow down for the draw's resources or for its work?
-    if (ablate & 128) {
+    if (ablated(ablate, 128)) {
         const uint64_t t0 = wall_clock64();
         while (wall_clock64() - t0 < 400000u) __builtin_amdgcn_s_sleep(64);
         if (lane == 0) {
@@ -703,7 +700,6 @@ __global__ __launch_bounds__(64 * WPG) void ransac_draw_kernel(const uint32_t* _
         }
         continue;
     }
-#endif
     const uint32_t n = (uint32_t)n64;
     const int kb = 32 - __builtin_clz(n);
     const bool pool = (int64_t)n <= ransac_setsize(k);
@@ -726,7 +722,7 @@ __global__ __launch_bounds__(64 * WPG) void ransac_draw_kernel(const uint32_t* _
     for (; s < trials; ++s) {
         IdxT* idx = sidx + ((int64_t)frame * trials + s) * k;
         int32_t* tr = TR && s < trace_trials ? trace + ((int64_t)frame * trace_trials + s) * (k + 3) : nullptr;
-        if (ablate & 16) {   // DIAGNOSTIC: no sample
+        if (ablated(ablate, 16)) {   // DIAGNOSTIC: no sample
         } else if (pool) {
             rb_sample_pool<IdxT, TR>(sh, st, n, k, idx, tr);
         } else {
@@ -760,7 +756,7 @@ __global__ __launch_bounds__(64 * WPG) void ransac_draw_kernel(const uint32_t* _
                 p2[c] = rb_readlane_f64(v, 3 * c + 1);
                 p3[c] = rb_readlane_f64(v, 3 * c + 2);
             }
-        } while (st.pos < kRBMaxDraws && !(ablate & 8) && rb_collinear(p1, p2, p3));
+        } while (st.pos < kRBMaxDraws && !ablated(ablate, 8) && rb_collinear(p1, p2, p3));
         if (st.pos >= kRBMaxDraws) {
             status = 2;
             break;
@@ -950,7 +946,7 @@ __device__ __forceinline__ void rb_wave_sum2_f64(double& a, double& b) {
 __device__ unsigned long long g_eval_phase[8];
 #define SVX_EVAL_STAMP(i)                                                                       \
     do {                                                                                        \
-        if ((ablate & 32) && tid == 0) {                                                        \
+        if (ablated(ablate, 32) && tid == 0) {                                                  \
             const uint64_t now_ = wall_clock64();                                               \
             atomicAdd(&g_eval_phase[i], (unsigned long long)(now_ - stamp_));                   \
             stamp_ = now_;                                                                      \
@@ -1000,8 +996,8 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
     }
     const int status = fstat[2 * frame], T = fstat[2 * frame + 1];
 #ifdef SVX_DIAG
-    uint64_t stamp_ = (ablate & 32) ? wall_clock64() : 0;
-    if ((ablate & 32) && tid == 0) atomicAdd(&g_eval_phase[6], 1ull);
+    uint64_t stamp_ = ablated(ablate, 32) ? wall_clock64() : 0;
+    if (ablated(ablate, 32) && tid == 0) atomicAdd(&g_eval_phase[6], 1ull);
 #endif
     const uint32_t* fpk = packed + (int64_t)frame * cap;
     const uint32_t* P = fpk;
@@ -1046,7 +1042,7 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
     SVX_EVAL_STAMP(0);
     // every trial's plane from its triple (the draw kernel wrote the three indices
     // into the record's first words), one lane a trial: the record in place
-    if (!(ablate & 1)) {
+    if (!ablated(ablate, 1)) {
         const uint32_t nm1 = (uint32_t)n64 - 1;
         for (int t = tid; t < T; t += kRBEvalThreads) {
             double* rec = ftri + (int64_t)t * kRBTri;
@@ -1073,7 +1069,7 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
     // the bound's 2^-18 (its sum in fp32, low by at most ~2^-20 relative) with a
     // margin of ~4x. (The reference's own fp64 roundings are ~2^-50 (T + 1).) The
     // lanes' sums are added in fp64.
-    if (!(ablate & 1)) {
+    if (!ablated(ablate, 1)) {
         // software-pipelined over the wave's trials: the next trial's indices and
         // record are loaded (global, just written by the draw kernel) while this
         // trial's points are gathered from LDS
@@ -1292,8 +1288,8 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
             double ex = rb_dpp_inf_f64<0x138>(inc);
             ex = lane == 0 ? carry : fmin(ex, carry);   // min over j < t
             bool c = in && !singular && !(e32 - eb > ex * (1.0 + 2e-9));   // NaN / inf: a candidate
-            if (ablate & 4) c = in && !singular;
-            if (ablate & 1) c = false;                                     // DIAGNOSTIC 1: no evaluation
+            if (ablated(ablate, 4)) c = in && !singular;
+            if (ablated(ablate, 1)) c = false;                                    // DIAGNOSTIC 1: no evaluation
             const uint64_t m = rb_ballot(c);
             if (c) cand[nc + __builtin_popcountll(m & ((1ull << lane) - 1))] = t;
             nc += (uint32_t)__builtin_popcountll(m);
@@ -1392,13 +1388,13 @@ static hipError_t launch_ransac_typed(const uint32_t* packed, const RbTables& tb
     // frame and LDS: the batched RANSAC 6.35 vs 6.93 ms with four against one a workgroup, the frame loop
     // 14.48-14.68 vs 14.72-14.79 ms (profiles/r06/ab_draw_wpg_s16.txt); eight against four: RANSAC equal, the loop
     // 14.54-14.66 vs 14.65-14.83 ms in five alternations on two boxes (ab_draw_wpg_s17.txt, _s18.txt);
-    // SVX_DRAW_WPG (diagnostic build) 1, 2, 4, 8 or 16
+    // SVX_DRAW_WPG (diagnostic build) 1, 2, 4 or 8: the sizes the LDS halving below reaches anyway
     int fpw = 1, wpg = 8;
     if (started)
         if (const char* e = svx_knob("SVX_DRAW_FPW")) fpw = std::max(1, std::atoi(e));
     if (const char* e = svx_knob("SVX_DRAW_WPG")) {
         const int v = std::atoi(e);
-        wpg = v == 1 || v == 2 || v == 8 || v == 16 ? v : 4;
+        wpg = v == 1 || v == 2 || v == 8 ? v : 4;
     }
     while (wpg > 1 && (trace || words * wpg > 16384)) wpg /= 2;   // traced: one wave a workgroup; dynamic LDS <= 64 KiB
     const int waves = (frames + fpw - 1) / fpw, grid = (waves + wpg - 1) / wpg;
@@ -1416,15 +1412,13 @@ static hipError_t launch_ransac_typed(const uint32_t* packed, const RbTables& tb
         SVX_DRAW(false, 4, nullptr, 0);
     } else if (wpg == 8) {
         SVX_DRAW(false, 8, nullptr, 0);
-    } else if (wpg == 16) {
-        SVX_DRAW(false, 16, nullptr, 0);
     } else {
         SVX_DRAW(false, 1, nullptr, 0);
     }
 #undef SVX_DRAW
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !(phases & 2)) return e;
-    if (ablate & (8 | 16)) ablate |= 1;   // DIAGNOSTIC: no samples / planes drawn -> no evaluation of them
+    if (ablated(ablate, 8 | 16)) ablate |= 1;   // DIAGNOSTIC: no samples / planes drawn -> no evaluation of them
     // eval LDS: the points when they fit beside the screen results (160 KiB per workgroup)
     // per trial: screened mean + bound (2 doubles), candidate index and its fp64 error
     const size_t scr = sizeof(double) * 2 * (size_t)trials + sizeof(int32_t) * ((size_t)trials + 1) +

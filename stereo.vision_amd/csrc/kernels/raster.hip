@@ -389,9 +389,10 @@ __global__ __launch_bounds__(256) void road_rowscan_kernel(const uint32_t* __res
     if (tid == 0) nzcount[frame] = all;
 }
 
-// RPW rows a wave (rows y0, y0 + 4, ...: the workgroup's four waves interleave): the next row's 32 words are
-// loaded (scalar) before this row's stores
-template <bool NT, bool NTI>
+// One row of road_rows_kernel. The image row and the walk's entries are ordinary stores: a pass's run starts at any
+// 8-byte offset, and the partial lines at its ends merge with the neighbouring passes' in L2 before they reach HBM;
+// written non-temporal each partial line went out on its own: 2.46 vs 2.99 ms per 4096 frames
+// (profiles/r04/ab_road_walk_nt.txt); the image rows too (2.40 vs 2.41-2.49 ms, profiles/r04/ab_road_img_nt.txt).
 __device__ __forceinline__ void road_row(const uint32_t (&ws)[kRbWords], uint32_t word, int32_t first, int frame,
                                          int y, int H,
                                          int64_t cap, uint8_t* __restrict__ img, int32_t* __restrict__ nzout,
@@ -406,10 +407,7 @@ __device__ __forceinline__ void road_row(const uint32_t (&ws)[kRbWords], uint32_
         q[i] = __builtin_amdgcn_perm(0u, 0u, ((__umul24(nib, 0x00204081u) & 0x01010101u) + 0x0C0C0C0Cu));
     }
     v4i* irow = reinterpret_cast<v4i*>(img + row * (kRbWords * 32) + 16 * lane);
-    if (NTI)
-        __builtin_nontemporal_store((v4i){(int)q[0], (int)q[1], (int)q[2], (int)q[3]}, irow);
-    else
-        *irow = (v4i){(int)q[0], (int)q[1], (int)q[2], (int)q[3]};
+    *irow = (v4i){(int)q[0], (int)q[1], (int)q[2], (int)q[3]};
     // the walk: [x, y] of the row's marked pixels in x order, from the row's first index. Pass i covers pixels
     // 64 i .. 64 i + 63, lane l pixel 64 i + l: its bit is bit l of words 2i, 2i+1 (scalar loads, the same for
     // the whole wave), its rank among the pass's marked pixels one v_mbcnt pair, and the pass's entries one
@@ -421,12 +419,7 @@ __device__ __forceinline__ void road_row(const uint32_t (&ws)[kRbWords], uint32_
         const uint32_t lo = ws[2 * i], hi = ws[2 * i + 1];
         const uint32_t mine = lane < 32 ? lo >> lane : hi >> (lane - 32);
         const uint32_t rank = __builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));
-        if (mine & 1u) {
-            if (NT)
-                __builtin_nontemporal_store(walk_pk(64 * i + lane, y), dst + base + rank);
-            else
-                dst[base + rank] = walk_pk(64 * i + lane, y);
-        }
+        if (mine & 1u) dst[base + rank] = walk_pk(64 * i + lane, y);
         base += __builtin_popcount(lo) + __builtin_popcount(hi);
     }
     if (paint) {   // imageRoadMap (stereovision.py:131-133): the lane's 16 pixels, 48 bytes
@@ -447,13 +440,16 @@ __device__ __forceinline__ void road_row(const uint32_t (&ws)[kRbWords], uint32_
     }
 }
 
-template <bool NT, bool NTI, int RPW>
+// kRoadRpw rows a wave (rows y0, y0 + 4, ...: the workgroup's four waves interleave): the next row's 32 words are
+// loaded (scalar) before this row's stores. 1 / 2 / 4 rows took 1.557 / 1.422 / 1.498 ms per 4096 frames in one
+// process (profiles/r05/probe_road_rpw_s8.txt).
+constexpr int kRoadRpw = 2;
 __global__ __launch_bounds__(256) void road_rows_kernel(const uint32_t* __restrict__ bits, int H,
                                                         const int32_t* __restrict__ roff, int64_t cap,
                                                         uint8_t* __restrict__ img, int32_t* __restrict__ nzout,
                                                         const uint8_t* __restrict__ bgr, uint8_t* __restrict__ paint) {
     const int frame = blockIdx.y;
-    int y = blockIdx.x * 4 * RPW + wave_uniform_id();
+    int y = blockIdx.x * 4 * kRoadRpw + wave_uniform_id();
     if (y >= H) return;
     const uint32_t* fb = bits + (int64_t)frame * H * kRbWords;   // wave-uniform addresses: scalar loads
     const int32_t* fo = roff + (int64_t)frame * H;
@@ -463,18 +459,18 @@ __global__ __launch_bounds__(256) void road_rows_kernel(const uint32_t* __restri
     uint32_t word = fb[y * kRbWords + (lane_id() >> 1)];   // the lane's own word (pixels 16 lane ..)
     int32_t first = fo[y];
 #pragma unroll
-    for (int r = 0; r < RPW; ++r) {
+    for (int r = 0; r < kRoadRpw; ++r) {
         const int yn = y + 4;
         uint32_t wn[kRbWords], wordn = 0;
         int32_t fn = 0;
-        const bool more = r + 1 < RPW && yn < H;   // uniform
+        const bool more = r + 1 < kRoadRpw && yn < H;   // uniform
         if (more) {
 #pragma unroll
             for (int i = 0; i < kRbWords; ++i) wn[i] = fb[yn * kRbWords + i];
             wordn = fb[yn * kRbWords + (lane_id() >> 1)];
             fn = fo[yn];
         }
-        road_row<NT, NTI>(ws, word, first, frame, y, H, cap, img, nzout, bgr, paint);
+        road_row(ws, word, first, frame, y, H, cap, img, nzout, bgr, paint);
         if (!more) break;
 #pragma unroll
         for (int i = 0; i < kRbWords; ++i) ws[i] = wn[i];
@@ -492,38 +488,8 @@ hipError_t launch_road_bits(const uint32_t* bits, int frames, int H, int W, int3
     hipLaunchKernelGGL(road_rowscan_kernel, dim3(frames), dim3(256), 0, s, bits, H, roff, nzcount);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    // The walk's entries as ordinary stores: a pass's run starts at any 8-byte offset, and the partial lines at
-    // its ends merge with the neighbouring passes' in L2 before they reach HBM; written non-temporal each partial
-    // line went out on its own: 2.46 vs 2.99 ms per 4096 frames (profiles/r04/ab_road_walk_nt.txt); the image
-    // rows too (2.40 vs 2.41-2.49 ms, profiles/r04/ab_road_img_nt.txt). A/B (diagnostic build): SVX_ROAD_NT=1 /
-    // SVX_ROAD_IMG_NT=1 make the walk / image stores non-temporal.
-    const char* nt = svx_knob("SVX_ROAD_NT");
-    const char* nti = svx_knob("SVX_ROAD_IMG_NT");
-    const bool wnt = nt && nt[0] == '1', int_ = nti && nti[0] == '1';
-    // rows a wave: 2 (SVX_ROAD_RPW, DIAGNOSTIC A/B: 1 / 2 / 4 took 1.557 / 1.422 / 1.498 ms per 4096 frames in one
-    // process, profiles/r05/probe_road_rpw_s8.txt)
-    const char* rk = svx_knob("SVX_ROAD_RPW");
-    const int rpw = rk ? std::atoi(rk) : 2;
-#define SVX_ROAD_ROWS(R)                                                                                            \
-    do {                                                                                                            \
-        const dim3 g((H + 4 * (R) - 1) / (4 * (R)), frames);                                                        \
-        if (wnt && int_)                                                                                            \
-            hipLaunchKernelGGL((road_rows_kernel<true, true, R>), g, dim3(256), 0, s, bits, H, roff, cap, img,     \
-                               nzout, bgr, paint);                                                                  \
-        else if (wnt)                                                                                               \
-            hipLaunchKernelGGL((road_rows_kernel<true, false, R>), g, dim3(256), 0, s, bits, H, roff, cap, img,    \
-                               nzout, bgr, paint);                                                                  \
-        else if (int_)                                                                                              \
-            hipLaunchKernelGGL((road_rows_kernel<false, true, R>), g, dim3(256), 0, s, bits, H, roff, cap, img,    \
-                               nzout, bgr, paint);                                                                  \
-        else                                                                                                        \
-            hipLaunchKernelGGL((road_rows_kernel<false, false, R>), g, dim3(256), 0, s, bits, H, roff, cap, img,   \
-                               nzout, bgr, paint);                                                                  \
-    } while (0)
-    if (rpw >= 4) SVX_ROAD_ROWS(4);
-    else if (rpw == 2) SVX_ROAD_ROWS(2);
-    else SVX_ROAD_ROWS(1);
-#undef SVX_ROAD_ROWS
+    hipLaunchKernelGGL(road_rows_kernel, dim3((H + 4 * kRoadRpw - 1) / (4 * kRoadRpw), frames), dim3(256), 0, s, bits,
+                       H, roff, cap, img, nzout, bgr, paint);
     return hipGetLastError();
 }
 

@@ -385,7 +385,7 @@ __device__ __forceinline__ void p2_load(P2Regs<STEP, QP, LC>& r, int c, int tid,
     const int ywl = (fastdiv40(min((c + 1) * per, p.frame_quads) - 1, p.Q_m40) * STEP) >> 5;
     // the window staged for the last chunk pass 2 ran still covers this one (same row word, keep1 range inside):
     // no delta loads and no stage writes (8192: DIAGNOSTIC A/B, always reload)
-    r.reuse = !(p.ablate & 8192) && r.staged && !(p.ablate & 1024) && p.dx_words <= 32 && ywl == ywb &&
+    r.reuse = !ablated(p.ablate, 8192 | 1024) && r.staged && p.dx_words <= 32 && ywl == ywb &&
               ywb == r.ywb && dmn >= r.dlo && dmx < r.dlo + kRDN;
     if (r.reuse) {
         r.narrow = true;
@@ -394,7 +394,7 @@ __device__ __forceinline__ void p2_load(P2Regs<STEP, QP, LC>& r, int c, int tid,
     r.staged = true;
     r.dlo = dlo;
     r.ywb = ywb;
-    r.narrow = !(p.ablate & 1024) && p.dx_words <= 32 && dmx - dlo < kRDN && ywl == ywb;   // 1024: DIAGNOSTIC A/B
+    r.narrow = !ablated(p.ablate, 1024) && p.dx_words <= 32 && dmx - dlo < kRDN && ywl == ywb;   // 1024: DIAGNOSTIC A/B
     if constexpr (LC) {   // transposed: words dlo >> 5 and the next of x = 4 tid .. 4 tid + 3 and of row 32 ywb + tid
         const int j0 = dlo >> 5, j1 = min(j0 + 1, 7);
         const int nx = 32 * p.dx_words, ny = 32 * p.dy_words;
@@ -487,26 +487,23 @@ __device__ __forceinline__ void p1_chunk(const P1Regs<STEP, QP, LC>& r, int c, u
     const uint32_t lim = p.hist_thr < 0 ? 0u : (uint32_t)p.hist_thr;
     constexpr int NPL = 4 * RCfg<STEP, QP, LC>::QPL;   // grid points a lane holds
     // density threshold in eighths (DIAGNOSTIC A/B: ablate bits 15-16 pick 6, 4, 5 or 7; release: 6)
-    const uint32_t dense8 = (0x7546u >> (4 * ((p.ablate >> 15) & 3))) & 0xFu;
-#ifdef SVX_DIAG
+    const uint32_t dense8 = (0x7546u >> (4 * ablate_field(p.ablate, 15, 3))) & 0xFu;
     // DIAGNOSTIC (diagnostic build only, results invalid): 2 no hue binning; 8 the bins without the atomics; 32
     // plain adds (no return) on spread bins (lane + 64 b mod 1000) without the bin arithmetic; 64 the real bins with
     // adds that return nothing (no candidates)
-    if (p.ablate & 2) {
-    } else if (p.ablate & (8 | 32 | 64)) {
+    if (ablated(p.ablate, 2)) {
+    } else if (ablated(p.ablate, 8 | 32 | 64)) {
         uint32_t acc = 0;
 #pragma unroll
         for (int b = 0; b < NPL; ++b) {
             if (!((keep >> b) & 1u)) continue;
-            if (p.ablate & 8) acc += r_bin_sel(r_col<STEP, QP, LC>(r.cw[b >> 2], b & 3));
-            else if (p.ablate & 64) __hip_atomic_fetch_add(&hist[r_bin_sel(r_col<STEP, QP, LC>(r.cw[b >> 2], b & 3))], 1u,
+            if (ablated(p.ablate, 8)) acc += r_bin_sel(r_col<STEP, QP, LC>(r.cw[b >> 2], b & 3));
+            else if (ablated(p.ablate, 64)) __hip_atomic_fetch_add(&hist[r_bin_sel(r_col<STEP, QP, LC>(r.cw[b >> 2], b & 3))], 1u,
                                                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             else atomicAdd(&hist[(uint32_t)(lane + 64 * b) % 1000u], 1u);
         }
         if (acc == 0xFFFFFFFFu) hist[0] = acc;   // keeps the bins
-    } else
-#endif
-    if (!(p.ablate & 16384) && wave_sum((uint32_t)__builtin_popcount(keep)) * 8u >= dense8 * 64u * NPL) {
+    } else if (!ablated(p.ablate, 16384) && wave_sum((uint32_t)__builtin_popcount(keep)) * 8u >= dense8 * 64u * NPL) {
         // uniform: a dense wave (>= 3/4 of its points kept, the road) bins its colours from registers, each lane
         // its own kept points in turn: at most 1/4 of the lanes idle, and no LDS staging writes and reads
         // (16384: DIAGNOSTIC A/B, always stage)
@@ -523,7 +520,7 @@ __device__ __forceinline__ void p1_chunk(const P1Regs<STEP, QP, LC>& r, int c, u
         }
     } else {
         const uint32_t wtotal = r_stage_colours_sel<STEP, QP, LC>(keep, r.cw, wstage, dump, pos0);
-        for (uint32_t j = lane; j < ((p.ablate & 512) ? 0u : wtotal); j += 4 * kWave) {   // four colours in flight
+        for (uint32_t j = lane; j < (ablated(p.ablate, 512) ? 0u : wtotal); j += 4 * kWave) {   // four colours in flight
             uint32_t o[4], cl[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) cl[k] = wstage[min(j + k * kWave, wtotal - 1)];   // the reads first
@@ -566,8 +563,7 @@ __device__ __forceinline__ void p2_write(const uint32_t* stage, uint32_t a, uint
         const uint32_t m = m0 + lane;
         if (m >= groups) continue;
         const uint32_t g = first + 4 * m;
-#ifdef SVX_DIAG
-        if (p.ablate & 4096) {   // DIAGNOSTIC (diagnostic build only, results invalid): the stores alone
+        if (ablated(p.ablate, 4096)) {   // DIAGNOSTIC (diagnostic build only, results invalid): the stores alone
             if (g >= a && g + 3 < b) {
                 const v4f z = {0.f, 0.f, 0.f, 0.f};
                 __builtin_nontemporal_store(z, reinterpret_cast<v4f*>(oX + g));
@@ -577,7 +573,6 @@ __device__ __forceinline__ void p2_write(const uint32_t* stage, uint32_t a, uint
             }
             continue;
         }
-#endif
         const uint4 u4 = *reinterpret_cast<const uint4*>(&stage[g & SM]);
         const uint32_t u[4] = {u4.x, u4.y, u4.z, u4.w};
         float X[4], Y[4], Z[4];
@@ -685,11 +680,7 @@ __device__ __forceinline__ void p2_chunk(P2Regs<STEP, QP, LC>& r, int c, bool mo
     if (!r.reuse) p2_stage_deltas<STEP, QP, LC>(r, dl);
     const int dlo = r.dlo;
     const bool narrow = r.narrow;
-#ifdef SVX_DIAG
-    const bool dirty_c = !(p.ablate & 16) && ((dirty[c >> 5] >> (c & 31)) & 1);   // 16: no chunk re-binned (invalid)
-#else
-    const bool dirty_c = (dirty[c >> 5] >> (c & 31)) & 1;
-#endif
+    const bool dirty_c = !ablated(p.ablate, 16) && ((dirty[c >> 5] >> (c & 31)) & 1);   // 16: no chunk re-binned
     if (dirty_c) {   // uniform: candidate chunk (rare)
         uint32_t cw[QPL][RCfg<STEP, QP, LC>::CW];
         r_load_bgr<STEP, QP, LC>(fbgr, r.g, p, cw);
@@ -884,7 +875,7 @@ __device__ __forceinline__ void frame_pass1(int frame, FusedShared<QP>& sh, cons
     __syncthreads();
     uint32_t nvalid = 0, nkept = 0;
     uint16_t* fkb = bf.kbits + (int64_t)frame * p.nchunks * 256;   // step 1: keep1 bits per chunk and lane
-    const int n1 = (p.ablate & 128) ? 0 : p.nchunks;   // ablate: DIAGNOSTIC ONLY
+    const int n1 = ablated(p.ablate, 128) ? 0 : p.nchunks;   // ablate: DIAGNOSTIC ONLY
     if constexpr (PF1) {   // chunk c + 1's loads in flight while chunk c is binned (pass 1 stores nothing)
         P1Regs<STEP, QP, LC> r1;
         if (n1 > 0) p1_load<STEP, QP, LC>(r1, 0, tid, fdisp, fbgr, p, false, chunk_any(sh, 0));
@@ -931,7 +922,7 @@ __device__ __forceinline__ void frame_pass2(int frame, FusedShared<QP>& sh, cons
     float* oZ = bf.oz + (int64_t)frame * bf.ofs;
     uint32_t* oPxy = bf.pxy + (int64_t)frame * bf.cap;
     uint32_t running = 0, flushed = 0;
-    const int n2 = (p.ablate & 256) ? 0 : p.nchunks;
+    const int n2 = ablated(p.ablate, 256) ? 0 : p.nchunks;
     // a chunk in which pass 1 kept no point (its keep1 range is 0 in every wave;
     // always so where the plane rules the chunk out) adds no output and is
     // skipped, loads included; the last chunk always runs (it flushes the tail)
@@ -984,15 +975,13 @@ __device__ __forceinline__ void fused_body(const PipeBuffers& bf, const RParams&
     const int frame = blockIdx.x;
     const FramePlane* Lp = bf.planes + (int64_t)frame * bf.plane_stride;
     const RLean L{Lp->al32, Lp->bb32, Lp->b032, Lp->tn32, Lp->g32};
-#ifdef SVX_DIAG
     // DIAGNOSTIC A/B (diagnostic build; outputs unchanged): ablate bits 20-30 = a start delay in us per slot group,
     // workgroup w of the first round waiting (w / 256) x that, so the five workgroups a CU holds do not run pass 1
     // and pass 2 in phase (the phase-lock probe)
-    if (const uint32_t us = (uint32_t)p.ablate >> 20; us && blockIdx.x < 5 * 256) {
+    if (const uint32_t us = ablate_field(p.ablate, 20, 0xFFFu); us && blockIdx.x < 5 * 256) {
         const uint64_t t0 = wall_clock64(), wait = (uint64_t)(blockIdx.x >> 8) * us * 100u;   // 100 MHz ticks
         while (wall_clock64() - t0 < wait) __builtin_amdgcn_s_sleep(32);
     }
-#endif
     frame_pass1<STEP, QP, LC, PF1>(frame, sh, bf, L, Lp, p);
     // pass 2 (store-bound) issues ahead of other workgroups' pass-1 waves on the SIMD: -0.2 to -0.4 %
     // (5.78 vs 5.80 ms, 6.81 vs 6.82 with per-frame planes; ten and eight in-process alternations)

@@ -487,9 +487,11 @@ __global__ __launch_bounds__(256) void sgbm_hsum_ring_kernel(SgbmK k, const uint
 // Vertical box sum with OpenCV's row rules, and the (0,-1) path.
 // ---------------------------------------------------------------------------
 // The operands of a path step never depend on the recurrence, so every walk
-// below keeps the next U steps' loads in flight (registers, clamped addresses:
-// the loads past a path's end are redundant) while it runs the current U steps.
-template <int U, bool DQ>
+// below keeps the next kSgPf steps' loads in flight (registers, clamped addresses:
+// the loads past a path's end are redundant) while it runs the current kSgPf
+// steps. 1 and 4 were slower and 16 no faster (retired knobs).
+constexpr int kSgPf = 8;
+template <bool DQ>
 __global__ __launch_bounds__(256) void sgbm_vertical_kernel(SgbmK k, const uint32_t* __restrict__ hvol,
                                                               uint32_t* __restrict__ cvol, uint32_t* __restrict__ l2vol,
                                                               uint8_t* __restrict__ q2vol, uint32_t* __restrict__ flags,
@@ -518,6 +520,7 @@ __global__ __launch_bounds__(256) void sgbm_vertical_kernel(SgbmK k, const uint3
         a = (hb + (size_t)min(y + SH2, H - 1) * rs)[lane];
         r = (hb + (size_t)min(max(y - SH2 - 1, 0), H - 1) * rs)[lane];
     };
+    constexpr int U = kSgPf;
     uint32_t ca[U], cr[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) load(u, ca[u], cr[u]);
@@ -648,7 +651,7 @@ __global__ __launch_bounds__(256) void sgbm_vertical_ring_kernel(SgbmK k, const 
 // ---------------------------------------------------------------------------
 // Diagonal paths: dir 1 from (x-1, y-1), dir 3 from (x+1, y-1).
 // ---------------------------------------------------------------------------
-template <int U, bool DQ>
+template <bool DQ>
 __global__ __launch_bounds__(256) void sgbm_diag_kernel(SgbmK k, const uint32_t* __restrict__ cvol,
                                                           uint32_t* __restrict__ l1vol, uint32_t* __restrict__ l3vol,
                                                           uint8_t* __restrict__ q1vol, uint8_t* __restrict__ q3vol,
@@ -684,6 +687,7 @@ __global__ __launch_bounds__(256) void sgbm_diag_kernel(SgbmK k, const uint32_t*
     const uint32_t st32 = (uint32_t)step;
     const auto cell = [&](int t) { return bld32(rc, lane * 4, (uint32_t)min(t, len - 1) * st32 * 4); };
     std::conditional_t<DQ, PathPk, PathState> st;
+    constexpr int U = kSgPf;
     uint32_t cc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) cc[u] = cell(u);
@@ -715,8 +719,10 @@ __global__ __launch_bounds__(256) void sgbm_diag_kernel(SgbmK k, const uint32_t*
 // ---------------------------------------------------------------------------
 // Row kernel: (-1,0) path + sum, (+1,0) path + selection, left-right check.
 // ---------------------------------------------------------------------------
-template <typename T>
-__device__ __forceinline__ T ld_nt(const T* p, bool nt) { return nt ? __builtin_nontemporal_load(p) : *p; }
+// The row walk's last-use accesses are non-temporal (26.40 vs 26.48 ms per 64 frames, faster in 4 of 5
+// alternations): the q-byte path's pass-B buffer loads and the int16 path's store of P. The int16 path's loads are
+// plain: written as `nt ? __builtin_nontemporal_load(p) : *p` they had always compiled to plain loads, and that is
+// what was measured.
 
 // LDS per wave: the right view's best cost per column as one word, (minS + 32768) << 16 | (0xFFFF - xi) — the
 // reference's "if (disp2cost[x2] > minS)" in decreasing x is the minimum of that key (the smaller cost, then
@@ -733,7 +739,7 @@ __host__ __device__ constexpr size_t sgbm_row_lds_per_wave(int W) { return ((siz
 #ifndef SVX_ROW_ABLATE
 #define SVX_ROW_ABLATE 0
 #endif
-template <int U0, bool NT, bool DQ>
+template <bool DQ>
 __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* __restrict__ cvol,
                                                          uint32_t* __restrict__ l1p, const uint32_t* __restrict__ l2vol,
                                                          const uint32_t* __restrict__ l3vol,
@@ -741,7 +747,7 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
                                                          const uint8_t* __restrict__ q2vol,
                                                          const uint8_t* __restrict__ q3vol, int16_t* __restrict__ d16,
                                                          uint32_t* __restrict__ flags, int frames) {
-    constexpr int UA = SVX_ROW_UA > 0 && DQ ? SVX_ROW_UA : U0, UB = SVX_ROW_UB > 0 && DQ ? SVX_ROW_UB : U0;
+    constexpr int UA = SVX_ROW_UA > 0 && DQ ? SVX_ROW_UA : kSgPf, UB = SVX_ROW_UB > 0 && DQ ? SVX_ROW_UB : kSgPf;
     extern __shared__ uint32_t rsm32[];
     const int wpb = blockDim.x >> 6, wave = wave_uniform_id();
     const int gw = blockIdx.x * wpb + wave;
@@ -778,9 +784,9 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
                 c = bld32(rc, lane * 4, (uint32_t)xi * 256);
             } else {
                 c = at(cvol, xi)[lane];
-                a = ld_nt(at(l1p, xi) + lane, NT);
-                b = ld_nt(at(l2vol, xi) + lane, NT);
-                e = ld_nt(at(l3vol, xi) + lane, NT);
+                a = at(l1p, xi)[lane];
+                b = at(l2vol, xi)[lane];
+                e = at(l3vol, xi)[lane];
             }
         };
 #pragma unroll
@@ -807,10 +813,7 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
                     path_step(lo16(cc[u]), hi16(cc[u]), sa, k.P1, k.P2, L0, L1);
                     const uint32_t pv = pack16(sat16(L0 + lo16(ca[u]) + lo16(cb[u]) + lo16(ce[u])),
                                                sat16(L1 + hi16(ca[u]) + hi16(cb[u]) + hi16(ce[u])));
-                    if (NT)
-                        __builtin_nontemporal_store(pv, at(l1p, xi) + lane);
-                    else
-                        at(l1p, xi)[lane] = pv;
+                    __builtin_nontemporal_store(pv, at(l1p, xi) + lane);
                 }
             }
 #pragma unroll
@@ -835,12 +838,12 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
             const int xi = max(n - 1 - j, 0);
             if constexpr (DQ) {
                 const uint32_t so = (uint32_t)xi * 64;
-                c = bld32(rc, lane * 4, so * 4, NT);
-                pp = bld8(rq0, lane, so, NT) | bld8(rq1, lane, so, NT) << 8 | bld8(rq2, lane, so, NT) << 16 |
-                     bld8(rq3, lane, so, NT) << 24;
+                c = bld32(rc, lane * 4, so * 4, true);
+                pp = bld8(rq0, lane, so, true) | bld8(rq1, lane, so, true) << 8 | bld8(rq2, lane, so, true) << 16 |
+                     bld8(rq3, lane, so, true) << 24;
             } else {
-                c = ld_nt(at(cvol, xi) + lane, NT);
-                pp = ld_nt(at(l1p, xi) + lane, NT);
+                c = at(cvol, xi)[lane];
+                pp = at(l1p, xi)[lane];
             }
         };
 #pragma unroll
@@ -1308,12 +1311,6 @@ hipError_t launch_copy_bgr_region(const uint8_t* src, int Hp, int Wp, uint8_t* d
     return hipGetLastError();
 }
 
-// steps each path walk keeps in flight (SVX_SGBM_PF: 1, 4 or 8; A/B only; 16 measured no faster)
-static int sgbm_prefetch() {
-    const char* e = svx_knob("SVX_SGBM_PF");
-    return e && *e ? std::atoi(e) : 8;
-}
-
 bool sgbm_supported(const SgbmK& k) {
     // the walks address a frame's volume through buffer resources with 32-bit byte offsets (wave_rsrc): a frame's
     // int16 volume, diagonal stride included, stays below 2^31 bytes
@@ -1360,14 +1357,9 @@ hipError_t launch_sgbm_compute(const SgbmK& k, const uint8_t* left, const uint8_
     const int cb = (k.width1 + 3) / 4;
     const int paths = 2 * (k.width1 + H - 1) * frames;
     const size_t lds4 = sgbm_row_lds_per_wave(k.W) * 4;
-    const int pf = sgbm_prefetch();
     // the register-ring vertical walk for the reference's block 21 (SVX_SGBM_VRING=0: the generic walk)
     const char* vr = svx_knob("SVX_SGBM_VRING");
     const bool vring = k.SH2 == 10 && !(vr && vr[0] == '0');
-    // non-temporal loads of the volumes the row walk reads for the last time, and of its P: 26.40 vs 26.48 ms per
-    // 64 frames, faster in 4 of 5 alternations (SVX_SGBM_NT=0: plain accesses; A/B)
-    const char* ntv = svx_knob("SVX_SGBM_NT");
-    const bool nt = !(ntv && ntv[0] == '0');
     // the q-byte volumes of the four directions the row walk sums (P2 <= 15; SVX_SGBM_DQ=0: int16 L volumes and
     // P, A/B): four volumes of 64 B a cell in the space of the fourth int16 volume
     const char* dqv = svx_knob("SVX_SGBM_DQ");
@@ -1377,29 +1369,21 @@ hipError_t launch_sgbm_compute(const SgbmK& k, const uint8_t* left, const uint8_
     uint8_t* q1 = q0 + qb;
     uint8_t* q2 = q1 + qb;
     uint8_t* q3 = q2 + qb;
-#define SVX_SGBM_WALKS(U, DQ)                                                                                     \
+#define SVX_SGBM_WALKS(DQ)                                                                                        \
     if (vring)                                                                                                    \
         hipLaunchKernelGGL((sgbm_vertical_ring_kernel<10, DQ>), dim3(frames * cb), dim3(256), 0, st, k, s.hl1,   \
                            s.c, s.l2, q2, s.flags, frames);                                                       \
     else                                                                                                          \
-        hipLaunchKernelGGL((sgbm_vertical_kernel<U, DQ>), dim3(frames * cb), dim3(256), 0, st, k, s.hl1, s.c,    \
-                           s.l2, q2, s.flags, frames);                                                            \
-    hipLaunchKernelGGL((sgbm_diag_kernel<U, DQ>), dim3((paths + 3) / 4), dim3(256), 0, st, k, s.c, s.hl1, s.l3,  \
-                       q1, q3, s.flags, frames);                                                                  \
-    if (nt)                                                                                                       \
-        hipLaunchKernelGGL((sgbm_row_kernel<U, true, DQ>), dim3((frames * H + 3) / 4), dim3(256), lds4, st, k,   \
-                           s.c, s.hl1, s.l2, s.l3, q0, q1, q2, q3, s.raw, s.flags, frames);                           \
-    else                                                                                                          \
-        hipLaunchKernelGGL((sgbm_row_kernel<U, false, DQ>), dim3((frames * H + 3) / 4), dim3(256), lds4, st, k,  \
-                           s.c, s.hl1, s.l2, s.l3, q0, q1, q2, q3, s.raw, s.flags, frames)
+        hipLaunchKernelGGL(sgbm_vertical_kernel<DQ>, dim3(frames * cb), dim3(256), 0, st, k, s.hl1, s.c, s.l2,   \
+                           q2, s.flags, frames);                                                                  \
+    hipLaunchKernelGGL(sgbm_diag_kernel<DQ>, dim3((paths + 3) / 4), dim3(256), 0, st, k, s.c, s.hl1, s.l3, q1,   \
+                       q3, s.flags, frames);                                                                      \
+    hipLaunchKernelGGL(sgbm_row_kernel<DQ>, dim3((frames * H + 3) / 4), dim3(256), lds4, st, k, s.c, s.hl1,      \
+                       s.l2, s.l3, q0, q1, q2, q3, s.raw, s.flags, frames)
     if (dq) {
-        SVX_SGBM_WALKS(8, true);
-    } else if (pf == 1) {
-        SVX_SGBM_WALKS(1, false);
-    } else if (pf == 4) {
-        SVX_SGBM_WALKS(4, false);
+        SVX_SGBM_WALKS(true);
     } else {
-        SVX_SGBM_WALKS(8, false);
+        SVX_SGBM_WALKS(false);
     }
 #undef SVX_SGBM_WALKS
     // StereoSGBM::compute's medianBlur(disp, disp, 3): raw -> d16 (grid: a frame's pixels x frames)

@@ -227,8 +227,7 @@ int sv_batch_create(int device, int frames, int H, int W, int step, int with_bgr
     sv_camera cam0{1, 1, 0, 0};
     b->kp = make_params(H, W, step, cam0, Wu);
     b->Ng = (int64_t)b->kp.Hg * b->kp.Wg;
-    b->cap = ((size_t)b->Ng + 63) / 64 * 64;
-    if (const char* e = svx_knob("SVX_CAP_PAD")) b->cap += (size_t)std::atoi(e) / 64 * 64;   // A/B: frame stride
+    b->cap = ((size_t)b->Ng + 63) / 64 * 64;   // (extra points between frames' outputs: no consistent effect, §4.1)
     b->dense_per_frame = (int64_t)b->kp.Hg * b->kp.pitch;
     const size_t px = (size_t)frames * H * W;
     hipError_t e = b->disp.ensure(px, false, 8);

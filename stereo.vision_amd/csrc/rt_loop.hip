@@ -168,25 +168,6 @@ static int loop_enqueue_tail(sv_loop* L, int64_t seq, uint64_t gate_epoch) {
     sv_batch* b = L->slot[(size_t)(seq % q.slots)];
     hipStream_t st = b->stream;
     if (gate_epoch) HIP_TRY(launch_loop_gate(L->gate.as<uint64_t>(), gate_epoch, 50.0, st));
-#ifdef SVX_DIAG
-    // DIAGNOSTIC probe (diagnostic build, SVX_LOOP_SIDE=1; results unchanged): one more fill pass over this batch's
-    // raw frames into a scratch buffer, on a side stream, beside the pipeline and the next batch's draw — how much
-    // does a pre-pass moved into that window slow them? (the three-deep front end)
-    if (const char* e = svx_knob("SVX_LOOP_SIDE"); e && e[0] == '1' && b->keep_input) {
-        static hipStream_t side = nullptr;
-        static hipEvent_t ev = nullptr;
-        static DevBuf scratch;
-        if (!side) {
-            HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        }
-        const int64_t px = (int64_t)b->H * b->W;
-        HIP_TRY(scratch.ensure((size_t)px * b->frames));
-        HIP_TRY(hipEventRecord(ev, st));
-        HIP_TRY(hipStreamWaitEvent(side, ev, 0));
-        HIP_TRY(launch_fill_prev(input_disp(b), scratch.as<uint8_t>(), nullptr, nullptr, nullptr, b->frames, px, side));
-    }
-#endif
     // the pipeline with every frame's own plane (stereovision.py:97-113)
     HIP_TRY(stage_begin(L, seq, kLsPipeline));
     if (int rc = sv_batch_pipeline_planes(b, &L->cam, q.point_thr, q.hist_thr, 0, 0)) return rc;
@@ -275,14 +256,9 @@ int sv_loop_submit(sv_loop* L, int64_t first_frame_id, int64_t* out_seq) {
     if (L->pending >= 0) {
         if (int rc = loop_enqueue_tail(L, L->pending, (uint64_t)seq + 1)) return rc;
     }
-    // RANSAC evaluation, after the previous batch's road pass (SVX_LOOP_EVAL_AFTER=pipeline, diagnostic build:
-    // after its pipeline, beside the road pass)
-    {   // (SVX_LOOP_EVAL_AFTER=none, diagnostic build: after this batch's draw only, so its workgroups take the CUs
-        // the previous batch's pipeline drains, beside that batch's road pass)
-        const char* ea = svx_knob("SVX_LOOP_EVAL_AFTER");
-        const int dep = ea && ea[0] == 'p' ? kLsPipeline : ea && ea[0] == 'n' ? -1 : kLsRoad;
-        if (seq > 0 && ps != s && dep >= 0) HIP_TRY(hipStreamWaitEvent(st, L->t1[ps][dep], 0));
-    }
+    // RANSAC evaluation, after the previous batch's road pass (after its pipeline, or after this batch's draw
+    // only, measured equal: DESIGN §8.2)
+    if (seq > 0 && ps != s) HIP_TRY(hipStreamWaitEvent(st, L->t1[ps][kLsRoad], 0));
     HIP_TRY(stage_begin(L, seq, kLsEval));
     if (int rc = batch_ransac_launch(b, &L->cam, q.seed_base, first_frame_id, q.trials, q.k, st, 2)) return rc;
     HIP_TRY(stage_end(L, seq, kLsEval));

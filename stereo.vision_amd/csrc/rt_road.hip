@@ -85,32 +85,25 @@ int sv_batch_road_raster(sv_batch* b, int sync) {
     HIP_TRY(b->road.ensure(px * b->frames));
     HIP_TRY(b->nz.ensure(sizeof(uint32_t) * b->cap * b->frames));   // packed entries x | y << 16 (walk_pk)
     HIP_TRY(b->nzcount.ensure(sizeof(int64_t) * b->frames));
-    // the images and their non-zero walks in one pass (road_kernel); SVX_ROAD_FUSED=0: raster, then the walk
-    const char* v = svx_knob("SVX_ROAD_FUSED");
-    b->nz_fresh = !(v && v[0] == '0');
+    // the images and their non-zero walks in one pass (memset + raster + walk measured slower)
     b->rmap_fresh = false;
     b->road_level = kRoadImages;
-    if (b->nz_fresh) {
-        uint8_t* paint = nullptr;
-        if (b->want_rmap) {   // imageRoadMap in the same pass (stereovision.py:131-133)
-            HIP_TRY(b->rmap.ensure(px * 3 * b->frames));
-            paint = b->rmap.as<uint8_t>();
-        }
-        if (b->rbits_fresh) {   // from the pipeline's bitmap (68 KB a frame) instead of its points (8 B a point)
-            HIP_TRY(b->roff.ensure(sizeof(int32_t) * (size_t)b->H * b->frames));
-            HIP_TRY(launch_road_bits(b->rbits.as<uint32_t>(), b->frames, b->H, b->W, b->roff.as<int32_t>(),
-                                     (int64_t)b->cap, b->road.as<uint8_t>(), b->nz.as<int32_t>(),
-                                     b->nzcount.as<int64_t>(), b->bgr.as<uint8_t>(), paint, b->stream));
-        } else {
-            HIP_TRY(launch_road(b->ppxy.as<uint32_t>(), b->counts, (int64_t)b->cap,
-                                b->road.as<uint8_t>(), b->frames, b->H, b->W, b->Wu, b->nz.as<int32_t>(),
-                                b->nzcount.as<int64_t>(), b->bgr.as<uint8_t>(), paint, b->stream));
-        }
-        b->rmap_fresh = paint != nullptr;
-    } else {
-        HIP_TRY(launch_raster(b->ppxy.as<int32_t>(), nullptr, 0, b->counts, 4, 2, (int64_t)b->cap,
-                              b->road.as<uint8_t>(), b->frames, b->H, b->W, b->Wu, b->stream));
+    uint8_t* paint = nullptr;
+    if (b->want_rmap) {   // imageRoadMap in the same pass (stereovision.py:131-133)
+        HIP_TRY(b->rmap.ensure(px * 3 * b->frames));
+        paint = b->rmap.as<uint8_t>();
     }
+    if (b->rbits_fresh) {   // from the pipeline's bitmap (68 KB a frame) instead of its points (8 B a point)
+        HIP_TRY(b->roff.ensure(sizeof(int32_t) * (size_t)b->H * b->frames));
+        HIP_TRY(launch_road_bits(b->rbits.as<uint32_t>(), b->frames, b->H, b->W, b->roff.as<int32_t>(),
+                                 (int64_t)b->cap, b->road.as<uint8_t>(), b->nz.as<int32_t>(),
+                                 b->nzcount.as<int64_t>(), b->bgr.as<uint8_t>(), paint, b->stream));
+    } else {
+        HIP_TRY(launch_road(b->ppxy.as<uint32_t>(), b->counts, (int64_t)b->cap, b->road.as<uint8_t>(), b->frames,
+                            b->H, b->W, b->Wu, b->nz.as<int32_t>(), b->nzcount.as<int64_t>(), b->bgr.as<uint8_t>(),
+                            paint, b->stream));
+    }
+    b->rmap_fresh = paint != nullptr;
     if (sync) HIP_TRY(hipStreamSynchronize(b->stream));
     return SV_OK;
 }
@@ -119,14 +112,7 @@ int sv_batch_nonzero(sv_batch* b, int sync) {
     if (!b) return fail(SV_E_ARG, "null batch");
     if (!b->road.p) return fail(SV_E_STATE, "no road images (sv_batch_road_raster first)");
     HIP_TRY(hipSetDevice(b->device));
-    if (b->nz_fresh) {   // sv_batch_road_raster walked the images it wrote
-        if (sync) HIP_TRY(hipStreamSynchronize(b->stream));
-        return SV_OK;
-    }
-    HIP_TRY(b->nz.ensure(sizeof(uint32_t) * b->cap * b->frames));   // packed entries x | y << 16 (walk_pk)
-    HIP_TRY(b->nzcount.ensure(sizeof(int64_t) * b->frames));
-    HIP_TRY(launch_nonzero(b->road.as<uint8_t>(), b->frames, (int64_t)b->H * b->W, b->W, b->nz.as<int32_t>(),
-                           (int64_t)b->cap, b->nzcount.as<int64_t>(), true, b->stream));
+    // sv_batch_road_raster walked the images as it wrote them: nothing left to launch
     if (sync) HIP_TRY(hipStreamSynchronize(b->stream));
     return SV_OK;
 }

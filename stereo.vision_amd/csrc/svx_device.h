@@ -28,6 +28,19 @@
 
 namespace svx {
 
+// The ablation words (KParams::ablate from SVX_ABLATE, the RANSAC kernels' `ablate` from SVX_RANSAC_ABLATE) are
+// read through these two alone. Diagnostic build: a test of the word's bits / the field (word >> shift) & mask.
+// Release: the constants false and 0, so an ablated branch is not in the release kernels at all.
+#ifdef SVX_DIAG
+__host__ __device__ constexpr bool ablated(int word, int bits) { return (word & bits) != 0; }
+__host__ __device__ constexpr uint32_t ablate_field(int word, int shift, uint32_t mask) {
+    return ((uint32_t)word >> shift) & mask;
+}
+#else
+__host__ __device__ constexpr bool ablated(int, int) { return false; }
+__host__ __device__ constexpr uint32_t ablate_field(int, int, uint32_t) { return 0; }
+#endif
+
 constexpr int kWave = 64;
 constexpr int kBins = 1024;   // hue bins 0..999 used; padded to 1024
 

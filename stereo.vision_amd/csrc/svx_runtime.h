@@ -214,7 +214,6 @@ struct sv_batch {
     bool pipe_placed = false;   // the resident pipeline's outputs were placed (pipe_place)
     DevBuf carmask;             // maskDisparity's 0x00/0xFF mask (H x W)
     DevBuf road, nz, nzcount;   // road images (frames x H x W), their non-zero walks (frames x cap x 2)
-    bool nz_fresh = false;      // nz holds the walk of the current road images (road_kernel wrote both)
     DevBuf rmap;                // imageRoadMap (stereovision.py:131-133): frames x H x W x 3, on request
     bool road_bits = false;     // the resident pipeline also writes the road bitmap (sv_batch_road_bits)
     bool rbits_fresh = false;   // rbits holds the bitmap of the current pipeline points
