@@ -210,6 +210,37 @@ int sv_min_circle_centre(const int32_t* pts, int64_t n, int32_t* out_xy);
 int sv_result_image(const uint8_t* bgr, const uint8_t* obstacles, const int32_t* hull_pts, int64_t n,
                     const sv_hull_info* info, int H, int W, uint8_t* out);
 
+/* ---- the image tile (stereovision.py:216, functions.py:452-499 batchImages) ---- */
+
+/* The picture performStereoVision returns as img_tile, shows and records: batchImages of [Disparity, ImageRoadMap,
+ * RoadImage, FilteredRoadImage, Result] with size = (H, W), every picture of the frame's size, so that resizeImage
+ * is a copy and a grey picture becomes BGR by repeating its byte:
+ *   S    = vstack(hstack(Disparity, ImageRoadMap), hstack(RoadImage, FilteredRoadImage))      2 H x 2 W x 3
+ *   l    = cv2.resize(S, (0, 0), fx=0.25, fy=0.25):
+ *          l[dy, dx, c] = (S[4dy+1, 4dx+1, c] + S[4dy+1, 4dx+2, c] + S[4dy+2, 4dx+1, c] + S[4dy+2, 4dx+2, c] + 2) >> 2
+ *   r    = cv2.resize(Result, (0, 0), fx=0.5, fy=0.5):
+ *          r[dy, dx, c] = (R[2dy, 2dx, c] + R[2dy, 2dx+1, c] + R[2dy+1, 2dx, c] + R[2dy+1, 2dx+1, c] + 2) >> 2
+ *   tile = hstack(l, r)                                                                        H / 2 x W x 3
+ * ImageRoadMap[y, x] = (0, 255, 0) where RoadImage[y, x] != 0, else the BGR (stereovision.py:131-133): it is not an
+ * input, its quadrant is painted from the road picture. H and W must be multiples of 4, 4 <= H, W <= 4096: the
+ * quadrants then meet on output-pixel boundaries (H / 4, W / 4) and no output pixel mixes two pictures. A road or
+ * cleaned picture of 0 and 255 gives quadrant bytes of {0, 64, 128, 191, 255}, by the number of its four samples
+ * that are set; other bytes are averaged as they are.
+ * Not built: tiles of frames whose H or W is no multiple of 4, the 390 x 889 cropped batch among them. There the
+ * reference first resizes its cropped pictures to 544 x 1024 with cv2.resize's general-scale bilinear filter, and
+ * that resize is not restated here. Tiles of one to four pictures are not built either.
+ * Parity with OpenCV is unpinned: cv2 is absent here. The argument for equality: INTER_LINEAR at scale 4 samples at
+ * 4 dx + 1.5, so both weights are 1/2 = 1024 / 2048 in its 11-bit fixed point, and at scale 2 it is the 2 x 2 area
+ * mean; all four weights are exactly 1/4, so any fixed-point or float implementation that rounds to nearest with
+ * ties up gives this byte (tests/tile_numpy.py restates the 8-bit fixed-point path for any scale and
+ * tests/test_tile_cpu.py checks it against the closed form). An implementation that rounds ties to even would
+ * differ where the sum mod 4 is 2. */
+/* One host frame, synchronous. disparity, road, cleaned: H x W u8; bgr, result: H x W x 3 u8; out: H / 2 x W x 3
+ * u8, (B, G, R) per pixel, overlapping no input. SV_E_ARG for a NULL pointer, an overlap, or H or W that is not a
+ * multiple of 4 in 4 .. 4096. */
+int sv_image_tile(const uint8_t* disparity, const uint8_t* bgr, const uint8_t* road, const uint8_t* cleaned,
+                  const uint8_t* result, int H, int W, uint8_t* out);
+
 /* ---- the stages a2-a6 one by one (the stage drop-ins) ---------------------- */
 
 /* calculatePointErrors (functions.py:300-312): out[i] = |(P_i . abc - 1) / d|
@@ -424,6 +455,21 @@ int sv_batch_result(sv_batch* b, int sync);
 int sv_batch_read_result(sv_batch* b, int frame, uint8_t* out);
 /* ms of the last sv_batch_result from HIP events on the batch stream. Synchronises the batch stream. */
 int sv_batch_result_ms(sv_batch* b, float* ms);
+/* The image tile (sv_image_tile) of every frame, on the device: one kernel that reads the batch's cleaned
+ * disparity (what sv_batch_read_disp returns), its BGR, the road picture, the cleaned road picture and the result
+ * image, and writes a buffer of its own. imageRoadMap's quadrant is painted from the road picture as it is read,
+ * so sv_batch_road_map need not be on. The two road pictures are read as packed bitmaps where the batch holds
+ * current ones (the clean-up's always, the pipeline's own after sv_batch_road_bits on 1024-wide frames), else as
+ * the u8 images; the bytes written are the same. The buffer holds frames x H / 2 rows of 3 W bytes with no
+ * padding, so one copy reads a tile or a run of tiles; it is allocated by the first call and takes 3.4 GB per
+ * 4096 frames of 544 x 1024. SV_E_STATE without a current result image (sv_batch_result after the last obstacle
+ * stage) or on a batch created without BGR; whatever invalidates the result invalidates the tile. SV_E_ARG unless
+ * H and W are multiples of 4 (4 .. 4096). */
+int sv_batch_tile(sv_batch* b, int sync);
+/* One frame's tile, H / 2 x W x 3 u8. */
+int sv_batch_read_tile(sv_batch* b, int frame, uint8_t* out);
+/* ms of the last sv_batch_tile from HIP events on the batch stream. Synchronises the batch stream. */
+int sv_batch_tile_ms(sv_batch* b, float* ms);
 
 /* Batched RANSAC (stereovision.py:84-94 for every frame):
  * maskpoints = the fp64 step-2 projection of the batch's disparity under the
@@ -547,7 +593,9 @@ typedef struct {
                             clean-up (sv_batch_road_clean; its mask: sv_loop_road_mask), 4 all of 3 + the
                             obstacle stage (sv_batch_road_hull; results: sv_batch_read_road_hull of the
                             batch sv_loop_batch returns), 5 all of 4 + the result image
-                            (sv_batch_result; sv_batch_read_result), inside the timeline's "road" stage */
+                            (sv_batch_result; sv_batch_read_result), 6 all of 5 + the image tile
+                            (sv_batch_tile; sv_batch_read_tile; H and W multiples of 4, checked by
+                            sv_loop_create), inside the timeline's "road" stage */
 } sv_loop_params;
 typedef struct sv_loop sv_loop;
 /* carmask: the grey H x W mask of maskDisparity (functions.py:35, :169-172), NULL for none. */

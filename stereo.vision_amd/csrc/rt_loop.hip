@@ -1,5 +1,6 @@
 // svx runtime: the software-pipelined frame loop (sv_loop) over the batch stages of the other units.
 #include "svx_runtime.h"
+#include "svx_tile_host.h"
 
 // ---------------------------------------------------------------------------
 // software-pipelined frame loop (stereovision.py:53-136 minus the cv2 drawing, over a sequence of batches)
@@ -77,9 +78,12 @@ int sv_loop_create(int device, const sv_loop_params* prm, const sv_camera* cam, 
     *out = nullptr;
     const sv_loop_params& q = *prm;
     if (q.frames < 1 || q.slots < 1 || q.slots > 8 || (q.source != 0 && q.source != 1) || q.prepass < 0 ||
-        q.prepass > 2 || q.road < 0 || q.road > 5 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
+        q.prepass > 2 || q.road < 0 || q.road > 6 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
         return fail(SV_E_ARG, "sv_loop_create: bad parameters (frames >= 1, 1 <= slots <= 8, source 0/1, prepass "
-                              "0..2, road 0..5, step 1/2, trials >= 0, k >= 1)");
+                              "0..2, road 0..6, step 1/2, trials >= 0, k >= 1)");
+    if (q.road == 6)   // the image tile's shape (sv_batch_tile would refuse it only after a batch's other stages)
+        if (const char* why = tile_check_shape(q.H, q.W))
+            return fail(SV_E_ARG, "sv_loop_create: road = 6 (the image tile) takes frames with %s", why);
     // what a submit would only find out after enqueueing the input and pre-pass stages (the RANSAC and synthetic
     // input limits of batch_ransac_prepare / sv_batch_synth)
     if (q.trials > 4096 || q.k > 1024) return fail(SV_E_ARG, "sv_loop_create: RANSAC trials <= 4096, k <= 1024");
@@ -183,8 +187,11 @@ static int loop_enqueue_tail(sv_loop* L, int64_t seq, uint64_t gate_epoch) {
     if (q.road >= 4) {   // the obstacle stage on the cleaned images (stereovision.py:170-189)
         if (int rc = sv_batch_road_hull(b, 0)) return rc;
     }
-    if (q.road == 5) {   // the result image from the BGR and the obstacle stage (stereovision.py:181-209)
+    if (q.road >= 5) {   // the result image from the BGR and the obstacle stage (stereovision.py:181-209)
         if (int rc = sv_batch_result(b, 0)) return rc;
+    }
+    if (q.road == 6) {   // batchImages' tile of the five pictures above (stereovision.py:216)
+        if (int rc = sv_batch_tile(b, 0)) return rc;
     }
     HIP_TRY(stage_end(L, seq, kLsRoad));
     if (L->pending == seq) L->pending = -1;

@@ -1,11 +1,13 @@
-// svx runtime: the road chain. Road raster + non-zero walk, sanitiseRoadImage's clean-up, the obstacle stage and
-// the result image, each as a host-frame drop-in and as a batch stage; the batch's stages form one chain whose
-// validity is the batch's road_level (svx_runtime.h).
+// svx runtime: the road chain. Road raster + non-zero walk, sanitiseRoadImage's clean-up, the obstacle stage, the
+// result image and the image tile, each as a host-frame drop-in and as a batch stage; the batch's stages form one
+// chain whose validity is the batch's road_level (svx_runtime.h).
 #include "svx_hull_host.h"
 #include "svx_morph.h"
 #include "svx_result.h"
 #include "svx_result_host.h"
 #include "svx_runtime.h"
+#include "svx_tile.h"
+#include "svx_tile_host.h"
 
 extern "C" {
 
@@ -573,6 +575,101 @@ int sv_batch_read_result(sv_batch* b, int frame, uint8_t* out) {
     const size_t px3 = (size_t)b->H * b->W * 3;
     HIP_TRY(hipMemcpy2D(out, (size_t)b->Wu * 3, b->rimg.as<uint8_t>() + px3 * frame, (size_t)b->W * 3,
                         (size_t)b->Wu * 3, b->H, hipMemcpyDeviceToHost));
+    return SV_OK;
+}
+
+// ---------------------------------------------------------------------------
+// the image tile (stereovision.py:216, functions.py:452-499 batchImages): kernels/tile.hip
+// ---------------------------------------------------------------------------
+static_assert(kTileHostMaxH == kTileMaxH && kTileHostMaxW == kTileMaxW, "svx_tile_host.h and svx_tile.h disagree");
+
+int sv_image_tile(const uint8_t* disparity, const uint8_t* bgr, const uint8_t* road, const uint8_t* cleaned,
+                  const uint8_t* result, int H, int W, uint8_t* out) {
+    if (const char* why = tile_check_args(disparity, bgr, road, cleaned, result, H, W, out))
+        return fail(SV_E_ARG, "sv_image_tile: bad arguments (%s)", why);
+    Locked L;
+    if (int rc = lock_current(L)) return rc;
+    Device* d = L.d;
+    hipStream_t s = d->stream;
+    const TileLayout l = tile_layout(H, W);
+    HIP_TRY(d->tile.ensure(l.bytes));
+    HIP_TRY(d->bgr.ensure(l.img));
+    uint8_t* base = d->tile.as<uint8_t>();
+    // the u8 pictures at the staging stride, the BGR and the result at the batch's (pad columns zero)
+    if (int rc = upload_u8(d->disp, disparity, H, W, l.pitch, s)) return rc;
+    if (int rc = upload_u8(d->aux, road, H, W, l.pitch, s)) return rc;
+    if (int rc = upload_u8(d->aux2, cleaned, H, W, l.pitch, s)) return rc;
+    if (l.pitch != W) {
+        HIP_TRY(hipMemsetAsync(d->bgr.p, 0, l.img, s));
+        HIP_TRY(hipMemsetAsync(base + l.off_res, 0, l.img, s));
+    }
+    HIP_TRY(hipMemcpy2DAsync(d->bgr.p, l.ld3, bgr, 3 * (size_t)W, 3 * (size_t)W, H, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpy2DAsync(base + l.off_res, l.ld3, result, 3 * (size_t)W, 3 * (size_t)W, H, hipMemcpyHostToDevice,
+                             s));
+    TileArgs a{};
+    a.disp = TilePlane{d->disp.p, 0, l.pitch};
+    a.bgr = TilePlane{d->bgr.p, 0, l.ld3};
+    a.road = TilePlane{d->aux.p, 0, l.pitch};
+    a.clean = TilePlane{d->aux2.p, 0, l.pitch};
+    a.res = TilePlane{base + l.off_res, 0, l.ld3};
+    a.H = H;
+    a.W = W;
+    HIP_TRY(launch_tile(a, 1, base + l.off_out, s));
+    HIP_TRY(hipMemcpyAsync(out, base + l.off_out, tile_frame_bytes(H, W), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return SV_OK;
+}
+
+int sv_batch_tile(sv_batch* b, int sync) {
+    if (!b) return fail(SV_E_ARG, "null batch");
+    if (!b->with_bgr) return fail(SV_E_STATE, "the image tile needs the batch's BGR (with_bgr)");
+    if (const char* why = tile_check_shape(b->H, b->Wu))
+        return fail(SV_E_ARG, "the image tile takes frames with %s (the batch's are %d x %d)", why, b->H, b->Wu);
+    if (int rc = need_level(b, kRoadResult, "no current result image (sv_batch_result first)")) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = b->stream;
+    hipEvent_t* tev;
+    HIP_TRY(stage_events(b, kEvTile, 2, &tev));
+    b->road_level = kRoadResult;
+    const int H = b->H, WW = (b->Wu + 31) / 32;
+    const int64_t px = (int64_t)H * b->W;
+    HIP_TRY(b->timg.ensure(tile_frame_bytes(H, b->Wu) * b->frames, false, 0, true));
+    TileArgs a{};
+    a.disp = TilePlane{b->disp.p, px, b->W};
+    a.bgr = TilePlane{b->bgr.p, 3 * px, 3 * b->W};
+    a.res = TilePlane{b->rimg.p, 3 * px, 3 * b->W};
+    // the two pictures of 0 and 255 from the packed bitmaps where the batch holds current ones: the clean-up's
+    // always, the pipeline's own (32 words a row) when it wrote one for the current points
+    if (b->rbits_fresh && b->Wu == 1024) a.rbits = TilePlane{b->rbits.p, 32 * (int64_t)H, 32};
+    else a.road = TilePlane{b->road.p, px, b->W};
+    a.cbits = TilePlane{b->cbits.p, (int64_t)H * WW, WW};
+    a.H = H;
+    a.W = b->Wu;
+    HIP_TRY(hipEventRecord(tev[0], s));
+    HIP_TRY(launch_tile(a, b->frames, b->timg.as<uint8_t>(), s));
+    HIP_TRY(hipEventRecord(tev[1], s));
+    b->road_level = kRoadTile;
+    if (sync) HIP_TRY(hipStreamSynchronize(s));
+    return SV_OK;
+}
+
+int sv_batch_tile_ms(sv_batch* b, float* ms) {
+    if (!b || !ms) return fail(SV_E_ARG, "null batch or ms");
+    if (int rc = need_level(b, kRoadTile, "no image tile (sv_batch_tile first)")) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    const hipEvent_t* tev = b->road_ev + kEvTile;
+    HIP_TRY(hipEventSynchronize(tev[1]));
+    HIP_TRY(hipEventElapsedTime(ms, tev[0], tev[1]));
+    return SV_OK;
+}
+
+int sv_batch_read_tile(sv_batch* b, int frame, uint8_t* out) {
+    if (!b || !out || frame < 0 || frame >= b->frames) return fail(SV_E_ARG, "bad args");
+    if (int rc = need_level(b, kRoadTile, "no image tile (sv_batch_tile first)")) return rc;
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    const size_t bytes = tile_frame_bytes(b->H, b->Wu);
+    HIP_TRY(hipMemcpy(out, b->timg.as<uint8_t>() + bytes * frame, bytes, hipMemcpyDeviceToHost));
     return SV_OK;
 }
 

@@ -143,6 +143,7 @@ struct Device {
     DevBuf mbits;                     // sv_sanitise_road: the image, the cleaned image and the mask as bitmaps
     DevBuf hull;                      // sv_road_obstacles: bitmaps, vertices and info (HullLayout)
     DevBuf res;                       // sv_result_image: image, obstacle bitmap, vertices and info (ResultLayout)
+    DevBuf tile;                      // sv_image_tile: the staged result image and the tile (TileLayout)
     DevBuf sg_l, sg_r, sg_out, sg_filt, sg_hist;   // host-frame SGBM / grey drop-ins
     SgbmBufs sg;
     Tables tables;
@@ -182,11 +183,12 @@ enum RoadLevel {
     kRoadImages,      // sv_batch_road_raster: road holds the images of the current points
     kRoadCleaned,     // sv_batch_road_clean: cbits / cimg / cnz hold the clean-up of those images
     kRoadObstacles,   // sv_batch_road_hull: hbuf holds the obstacle stage of that clean-up
-    kRoadResult       // sv_batch_result: rimg holds the result image of that obstacle stage
+    kRoadResult,      // sv_batch_result: rimg holds the result image of that obstacle stage
+    kRoadTile         // sv_batch_tile: timg holds the image tile of that result image
 };
 // the road chain's events in sv_batch::road_ev, made by a stage's first call: the clean-up's start, its kernel's
-// start / end and its end, then start / end of the obstacle stage and of the result image
-enum { kEvClean = 0, kEvHull = 4, kEvResult = 6, kEvRoadCount = 8 };
+// start / end and its end, then start / end of the obstacle stage, of the result image and of the image tile
+enum { kEvClean = 0, kEvHull = 4, kEvResult = 6, kEvTile = 8, kEvRoadCount = 10 };
 
 }  // namespace svx
 
@@ -219,7 +221,7 @@ struct sv_batch {
     bool rbits_fresh = false;   // rbits holds the bitmap of the current pipeline points
     DevBuf rbits, roff;         // the bitmap (frames x H x 32 words); the road pass's per-row walk offsets
     bool want_rmap = false, rmap_fresh = false;
-    RoadLevel road_level = kRoadNone;   // which of road / cimg / hbuf / rimg belong to the current pipeline points
+    RoadLevel road_level = kRoadNone;   // which of road / cimg / hbuf / rimg / timg belong to the current points
     hipEvent_t road_ev[kEvRoadCount] = {};
     // sanitiseRoadImage's clean-up (sv_batch_road_clean): the mask as a bitmap (behind its staged bytes), the packed
     // road images (when the pipeline wrote no bitmap), the cleaned bitmaps, images, walks (frames x ccap packed
@@ -235,6 +237,8 @@ struct sv_batch {
     HullPlane hull_shared{};
     // the result image (sv_batch_result): frames x H rows of 3 W bytes, the BGR's layout; made on first use
     DevBuf rimg;
+    // the image tile (sv_batch_tile): frames x H / 2 rows of 3 Wu bytes, packed; made on first use
+    DevBuf timg;
     DevBuf mpts, rres;          // one frame's maskpoints as fp64 (read-back scratch); counts + batched RANSAC results
     DevBuf prev0buf, rdbuf;     // the host prev0 of sv_batch_prepass; sv_batch_read_disp's masked frame (batch-owned:
                                 // the device-wide drop-in scratch is used on other streams)

@@ -89,6 +89,10 @@ SIGNATURES = {
     "sv_batch_result": [P, I],
     "sv_batch_read_result": [P, I, P],
     "sv_batch_result_ms": [P, PF],
+    "sv_image_tile": [P, P, P, P, P, I, I, P],
+    "sv_batch_tile": [P, I],
+    "sv_batch_read_tile": [P, I, P],
+    "sv_batch_tile_ms": [P, PF],
     "sv_point_errors": [P, I64, I64, P, P],
     "sv_hue_histogram": [P, I64, I64, P, P, P],
     "sv_select_less": [P, I64, D, P, PI64],

@@ -329,6 +329,24 @@ class Batch:
         _abi.call("sv_batch_read_result", self._h, frame, _abi.ptr(out))
         return out
 
+    def tile(self, sync=True):
+        """batchImages' tile (stereovision.py:216) of every frame, on the device: the cleaned disparity, imageRoadMap,
+        the road image and the cleaned road image at a quarter, the result image at a half; after result(), on a
+        batch with BGR whose H and W are multiples of 4 (sv_batch_tile)."""
+        _abi.call("sv_batch_tile", self._h, int(sync))
+
+    def tile_ms(self):
+        """ms of the last tile(), from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_tile_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
+    def read_tile(self, frame):
+        """One frame's tile, (H // 2, W, 3) uint8 BGR."""
+        out = np.empty((self.H // 2, self.W, 3), np.uint8)
+        _abi.call("sv_batch_read_tile", self._h, frame, _abi.ptr(out))
+        return out
+
     def ransac(self, seed_base, trials, k=600, first_frame=0, camera=None, sync=True):
         """RANSAC(maskpoints, trials) of every frame on the device (stereovision.py:84-94), frame F
         drawing what CPython draws after random.seed(seed_base + first_frame + F)."""

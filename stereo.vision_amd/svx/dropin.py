@@ -40,6 +40,9 @@ reference:
   circle; installed only with ``install(.., hull=True)``. ``road_obstacles`` gives the whole
   obstacle stage (hull, hull mask, obstacles, centre, glyph tip) of a cleaned road image,
   ``result_image`` the picture drawn from it (stereovision.py:181-209; array form only).
+* ``batchImages(imgList, size)`` (functions.py:456-501): the five-picture tile of
+  stereovision.py:216 on the GPU (``image_tile`` is its array form); other lists go to the
+  function it replaced. Installed only with ``install(.., tiles=True)``.
 * disparity pre-pass (functions.py:141-172): ``fillDisparity`` (new array, or
   the input itself when there is no previous frame), ``fillAltDisparity`` (in
   place, returns its argument), ``maskDisparity`` (new array; the mask is the
@@ -351,6 +354,66 @@ def result_image(imgL, obstacles, hull, centre=None, tip=None):  # noqa: N803
     return out
 
 
+# ---------------------------------------------------------------------------
+# the image tile (stereovision.py:216, functions.py:452-499)
+# ---------------------------------------------------------------------------
+def image_tile(disparity, imgL, road, cleaned, result):  # noqa: N803
+    """The img_tile of stereovision.py:216 on the GPU, (H // 2, W, 3) uint8 BGR: batchImages of the disparity,
+    imageRoadMap, the road image and the cleaned road image (a quarter each, left) and the result image (a half,
+    right). disparity, road, cleaned: (H, W) uint8; imgL, result: (H, W, 3) uint8; H and W multiples of 4, 4..4096.
+    imageRoadMap is imgL with (0, 255, 0) where road != 0 (stereovision.py:131-133), painted on the device
+    (include/svx.h, sv_image_tile); unpinned against cv2.resize."""
+    dp = np.ascontiguousarray(_as_u8(disparity, 2, "disparity"))
+    H, W = dp.shape
+    grey = [np.ascontiguousarray(_as_u8(a, 2, what)) for a, what in ((road, "road"), (cleaned, "cleaned"))]
+    bgr = [np.ascontiguousarray(_as_u8(a, 3, what)) for a, what in ((imgL, "image"), (result, "result"))]
+    for a, what in ((grey[0], "road"), (grey[1], "cleaned")):
+        if a.shape != (H, W):
+            raise ValueError(f"{what} shape {a.shape} != disparity shape {(H, W)}")
+    for a, what in ((bgr[0], "image"), (bgr[1], "result")):
+        if a.shape != (H, W, 3):
+            raise ValueError(f"{what} shape {a.shape} != {(H, W, 3)}")
+    out = np.empty((H // 2, W, 3), np.uint8)
+    _abi.call("sv_image_tile", _abi.ptr(dp), _abi.ptr(bgr[0]), _abi.ptr(grey[0]), _abi.ptr(grey[1]), _abi.ptr(bgr[1]),
+              H, W, _abi.ptr(out))
+    return out
+
+
+def _tile_images(imgList, size):  # noqa: N803
+    """The five arrays of a batchImages list that the device takes (grey, BGR, grey, grey, BGR uint8, all of shape
+    `size`, H and W multiples of 4, the second one already green wherever the third is set: what stereovision.py:216
+    passes), or None."""
+    try:
+        H, W = (int(v) for v in size)
+        imgs = [np.asarray(i[1]) for i in imgList]
+    except (TypeError, ValueError, IndexError):
+        return None
+    if len(imgs) != 5 or H % 4 or W % 4 or not (4 <= H <= 4096 and 4 <= W <= 4096):
+        return None
+    for a, colour in zip(imgs, (False, True, False, False, True)):
+        if a.dtype != np.uint8 or a.shape != ((H, W, 3) if colour else (H, W)):
+            return None
+    # sv_image_tile paints imageRoadMap's quadrant from the road image: the same bytes only for a map that is painted
+    if not (imgs[1][imgs[2] != 0] == (0, 255, 0)).all():
+        return None
+    return imgs
+
+
+def batchImages(imgList, size):  # noqa: N802,N803
+    """functions.py:456-501 for the list stereovision.py:216 passes: [(name, image)] of five images of shape `size`
+    (grey, BGR, grey, grey, BGR; H and W multiples of 4; the second the imageRoadMap of the third) becomes the tile
+    on the GPU (image_tile). Any other list goes to the function install() replaced, which needs cv2 as before;
+    without one, SvxError. Installed only with install(.., tiles=True)."""
+    imgs = _tile_images(imgList, size)
+    if imgs is not None:
+        return image_tile(*imgs)
+    orig = _saved.get("batchImages", _ABSENT)
+    if orig is _ABSENT or orig is None:
+        raise _abi.SvxError("batchImages: only five images of shape `size` (grey, BGR, grey, grey, BGR, H and W "
+                            "multiples of 4) are built on the device, and no function was replaced to take this list")
+    return orig(imgList, size)
+
+
 def getCenterPoint(points):  # noqa: N802
     """functions.py:418-421 with the exact circle: (int(x), int(y)) of the centre of the minimum enclosing circle of
     any (n, 1, 2) or (n, 2) integer points (|coordinate| <= 16383, at most 8192 distinct ones), computed in integers on the GPU. The reference's
@@ -397,13 +460,16 @@ MORPHOLOGY = ("sanitiseRoadImage",)
 # getCenterPoint (functions.py:418-421) returns the exact circle's centre where cv2.minEnclosingCircle approximates
 # in float32 (which way depends on its version): unpinned too, installed only with install(.., hull=True).
 HULL = ("getCenterPoint",)
+# batchImages (functions.py:456-501) restates cv2.resize at the two scales stereovision.py:216 uses (exact quarter
+# weights, include/svx.h): unpinned as well, installed only with install(.., tiles=True).
+TILES = ("batchImages",)
 ALIASES = {"project_disparity_to_3d": "projectDisparityTo3d",
            "project_3D_points_to_2D": "project3DPointsTo2DImagePoints"}
 _saved = {}
 _ABSENT = object()
 
 
-def install(functions_module, unpinned=False, morphology=False, hull=False):
+def install(functions_module, unpinned=False, morphology=False, hull=False, tiles=False):
     """Patch the reference's `functions` module in place (stereovision.py resolves
     f.<name> at call time, so performStereoVision picks the GPU path up).
 
@@ -414,12 +480,14 @@ def install(functions_module, unpinned=False, morphology=False, hull=False):
     reference's cv2 cannot be checked here. morphology=True also replaces
     sanitiseRoadImage (MORPHOLOGY: the road image's 9 x 9 close / erode / mask / close and its
     pixel walk, with the module's road_threshold_mask), a restatement of cv2 calls as well;
-    hull=True also replaces getCenterPoint (HULL) by the exact circle's centre."""
+    hull=True also replaces getCenterPoint (HULL) by the exact circle's centre; tiles=True
+    also replaces batchImages (TILES): the five-picture tile on the device, any other list
+    handed on to the module's own function."""
     global _module
     _abi.lib()  # fail loudly now if libsvx is missing
     _module = functions_module
     names = PINNED + (UNPINNED if unpinned else ()) + (MORPHOLOGY if morphology else ()) + \
-        (HULL if hull else ()) + tuple(ALIASES)
+        (HULL if hull else ()) + (TILES if tiles else ()) + tuple(ALIASES)
     for name in names:
         if name not in _saved:
             _saved[name] = getattr(functions_module, name, _ABSENT)

@@ -12,7 +12,8 @@ in batches and every batch runs the non-cv2 stages of that function:
              (road="clean": + sanitiseRoadImage's clean-up and its walk, functions.py:346-366;
               Batch.read_road_clean; road="obstacles": + the obstacle stage, stereovision.py:170-189;
               Batch.read_road_hull; road="result": + the result image, stereovision.py:181-209;
-              Batch.read_result)
+              Batch.read_result; road="tile": + batchImages' tile of the five pictures, stereovision.py:216;
+              Batch.read_tile)
 
 FrameLoop keeps `slots` batches in flight, one HIP stream each; a stage of batch k waits for the same stage of
 batch k - 1 (a device event), and the RANSAC evaluation of batch k for batch k - 1's road pass, so with two slots
@@ -39,7 +40,7 @@ from .batch import CAMERA, Batch
 STAGES = ("input", "prepass", "maskpoints", "draw", "eval", "pipeline", "road")
 _SOURCES = {"caller": 0, "synth": 1}
 _PREPASS = {"none": 0, "previous": 1, "mean": 2}
-_ROAD = {"none": 0, "walk": 1, "map": 2, "clean": 3, "obstacles": 4, "result": 5}
+_ROAD = {"none": 0, "walk": 1, "map": 2, "clean": 3, "obstacles": 4, "result": 5, "tile": 6}
 
 
 class FrameLoop:
@@ -68,8 +69,8 @@ class FrameLoop:
                 raise
 
     def road_mask(self, mask):
-        """The road_threshold_mask of road="clean" / "obstacles" / "result" (H x W uint8, non-zero keeps a pixel;
-        None: all ones), for the batches whose road stage is enqueued from now on (sv_loop_road_mask)."""
+        """The road_threshold_mask of road="clean" / "obstacles" / "result" / "tile" (H x W uint8, non-zero keeps a
+        pixel; None: all ones), for the batches whose road stage is enqueued from now on (sv_loop_road_mask)."""
         m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
         if m is not None and m.shape != (self.H, self.W):
             raise ValueError(f"road_mask shape {m.shape} != {(self.H, self.W)}")
