@@ -21,7 +21,7 @@
 //  * ransac_eval_kernel — one workgroup per frame: the frame's packed points
 //      staged in LDS; every trial's plane solved from its triple with numpy's
 //      rounding (the LAPACK dgesv + dot of functions.py:267 restated, round 3),
-//      every trial screened in fp32 from LDS (one wave per trial, a rigorous
+//      every trial screened in fp32 from LDS (eight lanes a trial, a rigorous
 //      bound to the fp64 mean), then the trials the screen cannot rule out
 //      evaluated in fp64 exactly as numpy does (the gemv's fmas, the pairwise
 //      sum of np.mean) and the first strict minimum kept (functions.py:289-293):
@@ -30,6 +30,7 @@
 //   bound by the screen's random 4-byte gathers: ~94 GB of sector traffic per
 //   4096 frames, the points of the ~4096 frames in flight not fitting L2.)
 #include "../svx_launch.h"
+#include "../svx_wave.h"
 
 namespace svx {
 
@@ -260,18 +261,9 @@ __device__ void rb_seed(uint32_t* mt, uint64_t seed) {
     mt[0] = 0x80000000u;
 }
 
-// Wave 0's lanes hand data to each other through LDS with no workgroup
-// barrier. The hardware keeps one wave's LDS operations in order, but the
-// compiler reasons per lane (lane i's store to mt[j] never aliases lane i's
-// load of mt[j - 35]) and may move loads above earlier stores: every hand-off
-// between lanes goes through this point (a compiler memory barrier + LDS wait).
-__device__ __forceinline__ void rb_wave_lds_sync() { __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ double rb_readlane_f64(double v, int l) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, l);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), l);
-    return __builtin_bit_cast(double, (uint64_t)hi << 32 | lo);
-}
+// A draw wave's lanes hand data to each other through LDS with no workgroup barrier: every such hand-off goes
+// through wave_lds_sync (svx_wave.h).
+
 // the wave's lane mask of a condition, straight from the compare (no 0/1 register in between)
 __device__ __forceinline__ uint64_t rb_ballot(bool c) { return __builtin_amdgcn_ballot_w64(c); }
 
@@ -279,13 +271,8 @@ __device__ __forceinline__ uint64_t rb_ballot(bool c) { return __builtin_amdgcn_
 // ((a & b) ^ c: truth table 0x6a)
 __device__ __forceinline__ uint32_t rb_temper(uint32_t y) {
     y ^= (y >> 11);
-#ifndef SVX_RB_NO_BITOP3
     y = __builtin_amdgcn_bitop3_b32(y << 7, 0x9d2c5680u, y, 0x6a);
     y = __builtin_amdgcn_bitop3_b32(y << 15, 0xefc60000u, y, 0x6a);
-#else
-    y ^= (y << 7) & 0x9d2c5680u;
-    y ^= (y << 15) & 0xefc60000u;
-#endif
     y ^= (y >> 18);
     return y;
 }
@@ -316,14 +303,14 @@ __device__ __forceinline__ void rb_twist_level(uint32_t* mt) {
         const uint32_t src = LEV == 0 ? mt[kk + 397] : mt[kk - 227];
         nv[j] = src ^ (y >> 1) ^ ((y & 1u) ? A : 0u);
     }
-    rb_wave_lds_sync();   // every read of this level before any write of it
+    wave_lds_sync();   // every read of this level before any write of it
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         int kk = lo + lane + 64 * j;
         if (lo + 64 * j + 63 >= hi) kk = min(kk, hi - 1);
         mt[kk] = nv[j];
     }
-    rb_wave_lds_sync();   // the next level reads this one's words
+    wave_lds_sync();   // the next level reads this one's words
 }
 
 // The stream without a copy of the outputs: the state words are advanced one
@@ -405,10 +392,8 @@ __device__ void rb_draw_below(RansacShared<IdxT>& sh, RbStream& st, uint32_t n, 
 // rejected. The k-th selection in stream order ends the sample and the stream
 // resumes right after it (bits claimed past it stay: the bitmap is cleared).
 // 192 draws a round; a round must fit the state's 624 positions (RbStream): span <= 397, i.e. up to 6 windows
-#ifndef SVX_RB_WIN
-#define SVX_RB_WIN 3
-#endif
-constexpr int kRBWin = SVX_RB_WIN;
+// (2, 4 and 6 windows: 8.43, 8.30, 8.38 against 8.27 ms, profiles/r03/ab_ransac_window.txt)
+constexpr int kRBWin = 3;
 static_assert(kRBWin >= 1 && 64 * kRBWin <= 397, "a round's draws must fit the MT state (RbStream)");
 
 template <class IdxT, bool TR>
@@ -477,12 +462,12 @@ __device__ void rb_sample_set(RansacShared<IdxT>& sh, RbStream& st, uint32_t n, 
         }
         have = q0 < k ? q0 : k;
         st.step(consumed);
-        rb_wave_lds_sync();   // the next round reads bits set/cleared by other lanes
+        wave_lds_sync();   // the next round reads bits set/cleared by other lanes
     }
     // clear the sample's bits (the whole bitmap, 16 bytes a store: the launch rounds it to 4 words)
     uint4* b4 = reinterpret_cast<uint4*>(sh.bitmap);
     for (uint32_t q = lane; q < (n + 127) / 128; q += kWave) b4[q] = make_uint4(0u, 0u, 0u, 0u);
-    rb_wave_lds_sync();
+    wave_lds_sync();
 }
 
 // wave 0: random.sample(range(n), k), pool branch (n <= setsize), over a virtual pool. CPython keeps
@@ -536,12 +521,11 @@ __device__ void rb_sample_pool(RansacShared<IdxT>& sh, RbStream& st, uint32_t n,
             ml[posj >= 0 ? (uint32_t)posj : cnt] = j | (vall << 16);
         }
         cnt += posj >= 0 ? 0u : 1u;
-        rb_wave_lds_sync();   // the next pick's scan reads lane 0's entry
+        wave_lds_sync();   // the next pick's scan reads lane 0's entry
     }
-    rb_wave_lds_sync();   // idx (and the trace) read by every lane next
+    wave_lds_sync();   // idx (and the trace) read by every lane next
 }
 
-[[maybe_unused]] constexpr int kRBGather = 10;     // screen gathers a lane keeps in flight
 constexpr int kRBEvalThreads = 1024;   // eval: 16 waves screen 16 trials at a time
 
 // One trial's record: the draw kernel writes the triple's three indices into
@@ -714,7 +698,7 @@ __global__ __launch_bounds__(64 * WPG) void ransac_draw_kernel(const uint32_t* _
     }
     for (int q = lane; q < bitmap_words; q += 64) sh.bitmap[q] = 0;
     if (lane == 0) rb_seed(sh.mt, seed_base + (uint64_t)(first_frame + frame));
-    rb_wave_lds_sync();   // the wave's own LDS: lane 0's seeding (and the clears) before every lane's reads
+    wave_lds_sync();   // the wave's own LDS: lane 0's seeding (and the clears) before every lane's reads
     RbStream st;
     const int g_pt = lane % 3, g_co = min(lane / 3, 2);   // the triple gather: point, coordinate (rb_point's tables)
     const uint32_t tg_y = (uint32_t)((tb.Y - tb.X) / 256), tg_z = (uint32_t)((tb.Z - tb.X) / 256);   // table rows
@@ -752,9 +736,9 @@ __global__ __launch_bounds__(64 * WPG) void ransac_draw_kernel(const uint32_t* _
             const double v = tb.X[row * 256 + dd];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                p1[c] = rb_readlane_f64(v, 3 * c + 0);
-                p2[c] = rb_readlane_f64(v, 3 * c + 1);
-                p3[c] = rb_readlane_f64(v, 3 * c + 2);
+                p1[c] = wave_readlane(v, 3 * c + 0);
+                p2[c] = wave_readlane(v, 3 * c + 1);
+                p3[c] = wave_readlane(v, 3 * c + 2);
             }
         } while (st.pos < kRBMaxDraws && !ablated(ablate, 8) && rb_collinear(p1, p2, p3));
         if (st.pos >= kRBMaxDraws) {
@@ -775,17 +759,8 @@ __global__ __launch_bounds__(64 * WPG) void ransac_draw_kernel(const uint32_t* _
         fstat[2 * frame] = status;   // 1: the reference would never return; 2: draw budget
         fstat[2 * frame + 1] = s;    // trials drawn (the failing one excluded)
     }
-    rb_wave_lds_sync();   // (the wave's own LDS) the next frame re-seeds mt and clears the bitmap
+    wave_lds_sync();   // (the wave's own LDS) the next frame re-seeds mt and clears the bitmap
     }
-}
-
-// A lane's value read by every lane (src uniform across the wave).
-__device__ __forceinline__ int rb_readlane(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
-__device__ __forceinline__ double rb_readlane(double v, int src) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)u, src);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(u >> 32), src);
-    return __builtin_bit_cast(double, (uint64_t)hi << 32 | lo);
 }
 
 // np.mean's sum of a trial's k distance terms (functions.py:289), by one wave, in
@@ -806,7 +781,7 @@ __device__ double rb_np_pairwise(int k, LoadF load, TermF term) {
     int sp = 1;
     int leaf_lo = 0, leaf_n = 0, nleaf = 0;   // leaf l in lane l
     while (sp > 0) {
-        const int lo = rb_readlane(st_lo, sp - 1), n = rb_readlane(st_n, sp - 1);
+        const int lo = wave_readlane(st_lo, sp - 1), n = wave_readlane(st_n, sp - 1);
         --sp;
         if (n <= 128) {
             if (lane == nleaf) {
@@ -866,15 +841,15 @@ __device__ double rb_np_pairwise(int k, LoadF load, TermF term) {
     st_n = k;
     sp = 1;
     while (sp > 0) {
-        const int lo = rb_readlane(st_lo, sp - 1), n = rb_readlane(st_n, sp - 1);
+        const int lo = wave_readlane(st_lo, sp - 1), n = wave_readlane(st_n, sp - 1);
         --sp;
         double push;
         if (n < 0) {   // both halves done: left + right
-            const double b = rb_readlane(vst, vsp - 1), a = rb_readlane(vst, vsp - 2);
+            const double b = wave_readlane(vst, vsp - 1), a = wave_readlane(vst, vsp - 2);
             vsp -= 2;
             push = a + b;
         } else if (n <= 128) {
-            push = rb_readlane(leafsum, li++);
+            push = wave_readlane(leafsum, li++);
         } else {
             const int n2 = n / 2 - (n / 2) % 8;
             if (lane == sp) st_n = -1;
@@ -892,50 +867,7 @@ __device__ double rb_np_pairwise(int k, LoadF load, TermF term) {
         if (lane == vsp) vst = push;
         ++vsp;
     }
-    return rb_readlane(vst, 0);
-}
-
-// One DPP step of an fp64 wave scan (both 32-bit halves moved with the same control; a lane whose source is
-// outside its row or row mask reads 0.0) and the two-value wave sum built from six of them — the wave_scan_dpp
-// pattern of svx_device.h (row_shr 1/2/4/8, then row_bcast 15 and 31; lane 63 ends with the total), the two
-// chains interleaved. One VALU op a move instead of a ds_bpermute round trip: the xor butterfly of __shfl_xor had
-// put six dependent LDS round trips on every trial's chain. All 64 lanes must be active. The additions run in
-// another order than the butterfly's; the screen's sums are bounded approximations (64 fp64 lane sums round by
-// ~2^-47 of their magnitude, far inside the screen's 4x margin) and the decision is taken on exact fp64 errors.
-template <int CTL, int RM>
-__device__ __forceinline__ double rb_dpp_f64(double v) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)u, CTL, RM, 0xf, false);
-    const uint32_t hi = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(uint32_t)(u >> 32), CTL, RM, 0xf, false);
-    return __builtin_bit_cast(double, (uint64_t)hi << 32 | lo);
-}
-// The DPP move of an fp64 value where a lane with no source (or outside the row mask) reads +inf, and the min-scan
-// step built from it.
-template <int CTL, int RM = 0xf>
-__device__ __forceinline__ double rb_dpp_inf_f64(double v) {
-    const uint64_t u = __builtin_bit_cast(uint64_t, v);
-    constexpr uint64_t kInf = 0x7FF0000000000000ull;
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)kInf, (int)(uint32_t)u, CTL, RM, 0xf, false);
-    const uint32_t hi =
-        (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(kInf >> 32), (int)(uint32_t)(u >> 32), CTL, RM, 0xf, false);
-    return __builtin_bit_cast(double, (uint64_t)hi << 32 | lo);
-}
-template <int CTL, int RM>
-__device__ __forceinline__ double rb_dpp_min_f64(double v) { return fmin(v, rb_dpp_inf_f64<CTL, RM>(v)); }
-
-__device__ __forceinline__ void rb_wave_sum2_f64(double& a, double& b) {
-#define SVX_RB_SUM2_STEP(ctl, rm)        \
-    a += rb_dpp_f64<ctl, rm>(a);         \
-    b += rb_dpp_f64<ctl, rm>(b)
-    SVX_RB_SUM2_STEP(0x111, 0xf);   // row_shr:1
-    SVX_RB_SUM2_STEP(0x112, 0xf);   // row_shr:2
-    SVX_RB_SUM2_STEP(0x114, 0xf);   // row_shr:4
-    SVX_RB_SUM2_STEP(0x118, 0xf);   // row_shr:8
-    SVX_RB_SUM2_STEP(0x142, 0xa);   // row_bcast:15
-    SVX_RB_SUM2_STEP(0x143, 0xc);   // row_bcast:31
-#undef SVX_RB_SUM2_STEP
-    a = rb_readlane_f64(a, 63);
-    b = rb_readlane_f64(b, 63);
+    return wave_readlane(vst, 0);
 }
 
 #ifdef SVX_DIAG
@@ -960,21 +892,13 @@ __device__ unsigned long long g_eval_phase[8];
 
 // Screen + decision. LDS: the frame's packed points (LDS_PTS) or none, then
 // per trial the screened mean and its bound (2 doubles).
-template <class IdxT, bool LDS_PTS>
 // 96 VGPRs (five waves' worth a SIMD, no spills) instead of the 123 the kernel takes unconstrained: its 1024-lane
 // workgroup is four waves a SIMD, and at 123 they filled the register file, so nothing else ran on a CU beside an
 // evaluation workgroup — in the frame loop the next batch's pre-pass waited for whole CUs (loop 15.30 -> 15.01 ms,
 // four alternations, profiles/r05/ab_eval_vgpr_s19.txt).
-#ifndef SVX_EVAL_WPE
-#define SVX_EVAL_WPE 5
-#endif
-#ifndef SVX_SCREEN_RUN   // index vectors a lane loads before gathering (the grouped screen)
-#define SVX_SCREEN_RUN 5
-#endif
-#ifndef SVX_SCREEN_GROUPED   // 0: the one-wave-a-trial screen (A/B build)
-#define SVX_SCREEN_GROUPED 1
-#endif
-__global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(SVX_EVAL_WPE))) void ransac_eval_kernel(
+constexpr int kRBEvalWavesPerEU = 5;
+template <class IdxT, bool LDS_PTS>
+__global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(kRBEvalWavesPerEU))) void ransac_eval_kernel(
     const uint32_t* __restrict__ packed, RbTables tb, int64_t cap, KParams cp,
     const int64_t* __restrict__ counts, int trials, int k, const IdxT* __restrict__ sidx,
     double* __restrict__ tri, const int32_t* __restrict__ fstat, double* __restrict__ out_abc,
@@ -1057,7 +981,7 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
         __syncthreads();   // the records are read by other waves below (same workgroup: same L1)
     }
     SVX_EVAL_STAMP(1);
-    // screen every trial in fp32 (one wave a trial): the mean distance from the
+    // screen every trial in fp32 (eight lanes a trial): the mean distance from the
     // packed points and, per point, the bound (T' + 1) 2^-18 / |abc| on its
     // difference to the fp64 distance, T' = rcp(d) (|cx Ba| + |cy Bb| + |Cc|) (the
     // term's magnitudes, ~ |Xa| + |Yb| + |Zc|; `point` below). A term's error:
@@ -1070,9 +994,6 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
     // margin of ~4x. (The reference's own fp64 roundings are ~2^-50 (T + 1).) The
     // lanes' sums are added in fp64.
     if (!ablated(ablate, 1)) {
-        // software-pipelined over the wave's trials: the next trial's indices and
-        // record are loaded (global, just written by the draw kernel) while this
-        // trial's points are gathered from LDS
         constexpr int NW = kRBEvalThreads / 64;
         // one point's fp32 distance term and bound term, summed per lane in fp32 (at most 10 terms a lane per
         // batch; the batches and the lanes in fp64): the sum's rounding, <= 9 x 2^-24 of the summed terms, stays
@@ -1089,29 +1010,23 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
             sum += live ? __builtin_fabsf(t) : 0.0f;
             bnd = __builtin_fmaf(rr, live ? q : 0.0f, bnd);
         };
-        [[maybe_unused]] const auto finish = [&](int t, const double (&rec)[kRBTri], double sum, double bnd) {
-            rb_wave_sum2_f64(sum, bnd);
-            if (lane == 0) {   // the screened mean and its bound; bound -1 marks a singular trial
-                const double inv = 1.0 / (rec[3] * k);   // (one more rounding each: inside the margin)
-                scr[2 * t] = sum * inv;
-                scr[2 * t + 1] = rec[4] == 1.0 ? -1.0 : (bnd + (double)k) * 0x1p-18 * inv;
-            }
-        };
-#if SVX_SCREEN_GROUPED
         // Eight lanes a trial, eight trials a wave pass: lane gl of a trial's group takes the trial's indices in
         // vectors of VEC (one 16-byte load each; the group's eight loads are one 128-byte line), RUN vectors a lane
         // loaded before any is used (two runs for k = 600 at 16-bit indices), then its VEC-point fp32 batches
         // (<= 10 terms each, as the bound requires) added in fp64; the group's sums meet in three DPP steps, eight
-        // trials at once, and the group's lane 0 stores the screened mean and bound. Against one wave a trial —
-        // ten 2-byte index loads a lane waited for once a trial and a 64-lane fp64 reduction and division on every
-        // trial's chain — the screen took 91 us a frame of the evaluation's 118, now 57 (RUN = 5: more spills
-        // VGPRs at the kernel's 96; RUN = 3: 70 us) (profiles/r06/probe_eval_phases_s18.txt,
+        // trials at once, and the group's lane 0 stores the screened mean and bound. The one-wave-a-trial screen
+        // this replaced — ten 2-byte index loads a lane waited for once a trial and a 64-lane fp64 reduction and
+        // division on every trial's chain — took 91 us a frame of the evaluation's 118, this one 57 (RUN = 5: more
+        // spills VGPRs at the kernel's 96; RUN = 3: 70 us) (profiles/r06/probe_eval_phases_s18.txt,
         // ab_eval_screen_grouped_s20.txt).
         {
             constexpr int GL = 8, TPW = kWave / GL;     // lanes a trial, trials a wave pass
             constexpr int VEC = 16 / (int)sizeof(IdxT);  // indices a 16-byte load holds
-            constexpr int RUN = SVX_SCREEN_RUN;          // loads a lane holds (k <= 8 x RUN x VEC in one run)
+            constexpr int RUN = 5;                       // loads a lane holds (k <= 8 x RUN x VEC in one run)
             const int grp = lane / GL, gl = lane % GL;
+            // every sample index is clamped to the frame's points before it addresses anything: the indices come
+            // from memory another kernel wrote, and a word past the frame's n points (a stale LDS word or another
+            // frame's) would send rb_point's table gathers (12-bit x, y fields) past the tables (DESIGN §7.2.1)
             const uint32_t nm1 = (uint32_t)n64 - 1;
             // 16-byte loads need every trial's row 16-byte aligned (k x sizeof(IdxT) a multiple of 16); a lane past
             // the row's end loads the row's last whole vector (k % VEC == 0 then) and its points are masked
@@ -1124,7 +1039,7 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
                 for (int q = 0; q < kRBTri; ++q) rec[q] = ftri[(int64_t)t * kRBTri + q];
                 const IdxT* idx = fidx + (int64_t)t * k;
                 double sum = 0.0, bnd = 0.0;
-                for (int r0 = 0; r0 < k; r0 += RUN * GL * VEC) {   // uniform: one run for k <= 640 (u16)
+                for (int r0 = 0; r0 < k; r0 += RUN * GL * VEC) {   // uniform: a run is RUN x GL x VEC indices, 320 at u16
                     uint4 w[RUN];   // the run's index vectors, unpacked where used
 #pragma unroll
                     for (int j = 0; j < RUN; ++j) {
@@ -1153,32 +1068,23 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
 #pragma unroll
                         for (int e = 0; e < VEC; ++e) {
                             const uint32_t ix = sizeof(IdxT) == 2 ? (ww[e / 2] >> (16 * (e % 2))) & 0xFFFFu : ww[e];
-#if defined(SVX_SCREEN_AB) && SVX_SCREEN_AB == 2   // DIAGNOSTIC A/B build (results invalid): no LDS gathers
-                            u[e] = min(ix, nm1) * 0x9E3779B1u | 0x01000000u;
-#else
                             u[e] = P[min(ix, nm1)];
-#endif
                         }
                         float s32 = 0.0f, b32 = 0.0f;
-#if defined(SVX_SCREEN_AB) && SVX_SCREEN_AB == 4   // DIAGNOSTIC A/B build (results invalid): no point arithmetic
-#pragma unroll
-                        for (int e = 0; e < VEC; ++e) s32 += (float)u[e];
-#else
 #pragma unroll
                         for (int e = 0; e < VEC; ++e) point(u[e], i + e < k, Ba, Bb, Cc, s32, b32);
-#endif
                         sum += (double)s32;
                         bnd += (double)b32;
                     }
                 }
                 // the group's eight lane sums: quad_perm [1,0,3,2] and [2,3,0,1], then the other quad of the
                 // half row (row_half_mirror); every lane of the group ends with the same total
-                sum += rb_dpp_f64<0xB1, 0xf>(sum);
-                bnd += rb_dpp_f64<0xB1, 0xf>(bnd);
-                sum += rb_dpp_f64<0x4E, 0xf>(sum);
-                bnd += rb_dpp_f64<0x4E, 0xf>(bnd);
-                sum += rb_dpp_f64<0x141, 0xf>(sum);
-                bnd += rb_dpp_f64<0x141, 0xf>(bnd);
+                sum += dpp_move<0xB1>(sum, 0.0);
+                bnd += dpp_move<0xB1>(bnd, 0.0);
+                sum += dpp_move<0x4E>(sum, 0.0);
+                bnd += dpp_move<0x4E>(bnd, 0.0);
+                sum += dpp_move<0x141>(sum, 0.0);
+                bnd += dpp_move<0x141>(bnd, 0.0);
                 if (gl == 0 && t0 + grp < T) {   // the screened mean and its bound; bound -1 marks a singular trial
                     const double inv = 1.0 / (rec[3] * k);
                     scr[2 * t] = sum * inv;
@@ -1186,68 +1092,6 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
                 }
             }
         }
-#else
-        {
-            // every sample index is clamped to the frame's points before it addresses anything: the indices come
-            // from memory another kernel wrote, and a word past the frame's n points (a stale LDS word or another
-            // frame's) would send rb_point's table gathers (12-bit x, y fields) past the tables (DESIGN §7.2.1)
-            const uint32_t nm1 = (uint32_t)n64 - 1;
-            auto load = [&](int t, uint32_t (&ix)[kRBGather], double (&rec)[kRBTri]) {
-                const IdxT* idx = fidx + (int64_t)t * k;
-#if defined(SVX_SCREEN_AB) && SVX_SCREEN_AB == 1   // DIAGNOSTIC A/B build (results invalid): the first trial's indices only
-                if (t < NW)
-#endif
-#pragma unroll
-                for (int v = 0; v < kRBGather; ++v)
-                    ix[v] = min((uint32_t)idx[min(lane + kWave * v, k - 1)], nm1);   // no branch
-#pragma unroll
-                for (int q = 0; q < kRBTri; ++q) rec[q] = ftri[(int64_t)t * kRBTri + q];
-            };
-            uint32_t nix[kRBGather];
-            double nrec[kRBTri];
-            if (wave < T) load(wave, nix, nrec);
-            for (int t = wave; t < T; t += NW) {
-                uint32_t ix[kRBGather];
-                double rec[kRBTri];
-#pragma unroll
-                for (int v = 0; v < kRBGather; ++v) ix[v] = nix[v];
-#pragma unroll
-                for (int q = 0; q < kRBTri; ++q) rec[q] = nrec[q];
-                if (t + NW < T) load(t + NW, nix, nrec);
-                double sum = 0.0, bnd = 0.0;
-                if (rec[4] != 1.0) {
-                    const double Ba64 = cp.B * rec[0], Bb64 = cp.B * rec[1];
-                    const float Ba = (float)Ba64, Bb = (float)Bb64;
-                    const float Cc = (float)(cp.fB * rec[2] - (double)cp.cw_lo * Ba64 - (double)cp.ch_lo * Bb64);
-                    for (int j0 = lane, g = 0; j0 < k + lane; j0 += kRBGather * kWave, ++g) {   // uniform
-                        uint32_t u[kRBGather];
-                        float s32 = 0.0f, b32 = 0.0f;
-                        if (g > 0) {   // k > 640: the rest of the sample (same order as the first batch)
-#pragma unroll
-                            for (int v = 0; v < kRBGather; ++v)
-                                ix[v] = min((uint32_t)fidx[(int64_t)t * k + min(j0 + kWave * v, k - 1)], nm1);
-                        }
-#if defined(SVX_SCREEN_AB) && SVX_SCREEN_AB == 2   // DIAGNOSTIC A/B build (results invalid): no LDS gathers
-#pragma unroll
-                        for (int v = 0; v < kRBGather; ++v) u[v] = ix[v] * 0x9E3779B1u;
-#else
-#pragma unroll
-                        for (int v = 0; v < kRBGather; ++v) u[v] = P[ix[v]];
-#endif
-#pragma unroll
-                        for (int v = 0; v < kRBGather; ++v) point(u[v], j0 + kWave * v < k, Ba, Bb, Cc, s32, b32);
-                        sum += (double)s32;
-                        bnd += (double)b32;
-                    }
-                }
-#if defined(SVX_SCREEN_AB) && SVX_SCREEN_AB == 3   // DIAGNOSTIC A/B build (results invalid): no wave sums
-                if (lane == 0) scr[2 * t] = sum, scr[2 * t + 1] = bnd;
-#else
-                finish(t, rec, sum, bnd);
-#endif
-            }
-        }
-#endif
     } else {
         for (int t = tid; t < T; t += kRBEvalThreads) scr[2 * t + 1] = ftri[(int64_t)t * kRBTri + 4] == 1.0 ? -1.0 : 0.0;
     }
@@ -1278,14 +1122,16 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
             const double ub = (in && !singular) ? e32 + eb : __builtin_huge_val();
             // inclusive min-scan over the wave by DPP (row_shr 1/2/4/8, row_bcast 15/31; a lane with no source keeps
             // +inf), then the exclusive one by wave_shr:1 — six VALU moves instead of six ds_bpermute round trips
+            // (svx_wave.h's ladder spelled out: through wave_scan the diagnostic build's LDS_PTS instances keep their
+            // vector code but allocate one scalar register differently, and the kernels' bytes are held equal)
             double inc = ub;
-            inc = rb_dpp_min_f64<0x111, 0xf>(inc);
-            inc = rb_dpp_min_f64<0x112, 0xf>(inc);
-            inc = rb_dpp_min_f64<0x114, 0xf>(inc);
-            inc = rb_dpp_min_f64<0x118, 0xf>(inc);
-            inc = rb_dpp_min_f64<0x142, 0xa>(inc);
-            inc = rb_dpp_min_f64<0x143, 0xc>(inc);
-            double ex = rb_dpp_inf_f64<0x138>(inc);
+            inc = fmin(inc, dpp_move<0x111, 0xf>(inc, __builtin_huge_val()));
+            inc = fmin(inc, dpp_move<0x112, 0xf>(inc, __builtin_huge_val()));
+            inc = fmin(inc, dpp_move<0x114, 0xf>(inc, __builtin_huge_val()));
+            inc = fmin(inc, dpp_move<0x118, 0xf>(inc, __builtin_huge_val()));
+            inc = fmin(inc, dpp_move<0x142, 0xa>(inc, __builtin_huge_val()));
+            inc = fmin(inc, dpp_move<0x143, 0xc>(inc, __builtin_huge_val()));
+            double ex = dpp_move<0x138>(inc, __builtin_huge_val());
             ex = lane == 0 ? carry : fmin(ex, carry);   // min over j < t
             bool c = in && !singular && !(e32 - eb > ex * (1.0 + 2e-9));   // NaN / inf: a candidate
             if (ablated(ablate, 4)) c = in && !singular;
@@ -1294,7 +1140,7 @@ __global__ __launch_bounds__(kRBEvalThreads) __attribute__((amdgpu_waves_per_eu(
             if (c) cand[nc + __builtin_popcountll(m & ((1ull << lane) - 1))] = t;
             nc += (uint32_t)__builtin_popcountll(m);
             sing |= rb_ballot(singular) != 0 ? 1u : 0u;
-            carry = fmin(carry, rb_readlane_f64(inc, kWave - 1));
+            carry = fmin(carry, wave_readlane(inc, kWave - 1));
         }
         if (lane == 0) {
             ncand_s = nc;

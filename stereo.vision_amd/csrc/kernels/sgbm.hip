@@ -29,6 +29,7 @@
 
 #include "../svx_device.h"
 #include "../svx_sgbm.h"
+#include "../svx_wave.h"
 
 namespace svx {
 namespace {
@@ -41,19 +42,10 @@ __device__ __forceinline__ int hi16(uint32_t v) { return (int)(int16_t)(v >> 16)
 __device__ __forceinline__ uint32_t pack16(int a, int b) { return (uint32_t)(uint16_t)a | ((uint32_t)(uint16_t)b << 16); }
 __device__ __forceinline__ int sat16(int v) { return v < kInt16Min ? kInt16Min : (v > kMaxCost ? kMaxCost : v); }
 __device__ __forceinline__ bool out16(int v) { return v < kInt16Min || v > kMaxCost; }
-// Lane hand-offs through LDS inside one wave: the hardware keeps a wave's LDS
-// operations in order; this keeps the compiler from moving loads above them.
-__device__ __forceinline__ void wave_lds_sync() { __asm__ volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
 
 // min over the wave (signed), every lane active: inclusive DPP min-scan, lane 63.
 __device__ __forceinline__ int wave_min_i32(int v) {
-    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x111, 0xf, 0xf, false));   // row_shr:1
-    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x112, 0xf, 0xf, false));   // row_shr:2
-    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x114, 0xf, 0xf, false));   // row_shr:4
-    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x118, 0xf, 0xf, false));   // row_shr:8
-    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x142, 0xa, 0xf, false));   // row_bcast:15
-    v = min(v, __builtin_amdgcn_update_dpp(0x7fffffff, v, 0x143, 0xc, 0xf, false));   // row_bcast:31
-    return __builtin_amdgcn_readlane(v, 63);
+    return wave_readlane(wave_scan(v, 0x7fffffff, [](int a, int b) { return min(a, b); }), 63);
 }
 
 // One step of a path (OpenCV formula 13): lane l holds d0 = 2l, d1 = 2l + 1.
@@ -73,8 +65,8 @@ struct PathState {
 // both DPP scans interleaved: path_l gives L and min(L0, L1) of the lane, path_commit takes the wave's min.
 __device__ __forceinline__ int path_l(int c0, int c1, const PathState& s, int P1, int P2, int& L0, int& L1) {
     const int delta = s.pmin + P2;
-    const int left = __builtin_amdgcn_update_dpp(kMaxCost, s.p1, 0x138, 0xf, 0xf, false);   // wave_shr:1, d0 - 1
-    const int right = __builtin_amdgcn_update_dpp(kMaxCost, s.p0, 0x130, 0xf, 0xf, false);  // wave_shl:1, d1 + 1
+    const int left = dpp_move<0x138>(s.p1, kMaxCost);    // wave_shr:1, d0 - 1
+    const int right = dpp_move<0x130>(s.p0, kMaxCost);   // wave_shl:1, d1 + 1
     const int m0 = min(min(s.p0, delta), min(left, s.p1) + P1);
     const int m1 = min(min(s.p1, delta), min(s.p0, right) + P1);
     L0 = c0 + m0 - delta;
@@ -110,8 +102,8 @@ struct PathPk {
 __device__ __forceinline__ uint32_t pk_l(uint32_t c, const PathPk& s, int P1, int P2, uint32_t& q, int& lm) {
     const int delta = s.pmin + P2;
     const short ds = (short)min(delta, kMaxCost), dw = (short)delta;
-    const uint32_t sh = (uint32_t)__builtin_amdgcn_update_dpp(0x7FFF7FFF, (int)s.p, 0x138, 0xf, 0xf, false);  // lane - 1
-    const uint32_t sl = (uint32_t)__builtin_amdgcn_update_dpp(0x7FFF7FFF, (int)s.p, 0x130, 0xf, 0xf, false);  // lane + 1
+    const uint32_t sh = dpp_move<0x138>(s.p, 0x7FFF7FFFu);   // lane - 1
+    const uint32_t sl = dpp_move<0x130>(s.p, 0x7FFF7FFFu);   // lane + 1
     const pk16 lft = as_pk(__builtin_amdgcn_alignbit(s.p, sh, 16));   // (d0 - 1, d1 - 1) = (sh.hi, p.lo)
     const pk16 rgt = as_pk(__builtin_amdgcn_alignbit(sl, s.p, 16));   // (d0 + 1, d1 + 1) = (p.hi, sl.lo)
     const pk16 n1 = __builtin_elementwise_add_sat(__builtin_elementwise_min(lft, rgt), (pk16){(short)P1, (short)P1});
@@ -158,18 +150,9 @@ __device__ __forceinline__ void bst8(uint8_t v, __amdgpu_buffer_rsrc_t r, uint32
 
 // two wave minimums, their DPP steps interleaved (each step's input was written two instructions earlier)
 __device__ __forceinline__ void wave_min2_i32(int a, int b, int& ra, int& rb) {
-#define SVX_MIN2_STEP(ctl, rm)                                                                 \
-    a = min(a, __builtin_amdgcn_update_dpp(0x7fffffff, a, ctl, rm, 0xf, false));               \
-    b = min(b, __builtin_amdgcn_update_dpp(0x7fffffff, b, ctl, rm, 0xf, false))
-    SVX_MIN2_STEP(0x111, 0xf);
-    SVX_MIN2_STEP(0x112, 0xf);
-    SVX_MIN2_STEP(0x114, 0xf);
-    SVX_MIN2_STEP(0x118, 0xf);
-    SVX_MIN2_STEP(0x142, 0xa);
-    SVX_MIN2_STEP(0x143, 0xc);
-#undef SVX_MIN2_STEP
-    ra = __builtin_amdgcn_readlane(a, 63);
-    rb = __builtin_amdgcn_readlane(b, 63);
+    wave_scan2(a, b, 0x7fffffff, [](int x, int y) { return min(x, y); });
+    ra = wave_readlane(a, 63);
+    rb = wave_readlane(b, 63);
 }
 
 // A path's L minus the cost it adds, as OpenCV computes it, is min(...) - delta
@@ -563,9 +546,6 @@ __global__ __launch_bounds__(256) void sgbm_vertical_kernel(SgbmK k, const uint3
 // read once: the row a step drops (max(y - SH2 - 1, 0)) is the row added RS = 2 SH2 + 1 steps before it, or
 // one of rows 0 .. SH2 read for the first window, so the walk keeps the next RS drops in registers (a ring
 // indexed by the unrolled step) and loads only the added rows, the next block's in flight.
-#ifndef SVX_VRING_ABLATE
-#define SVX_VRING_ABLATE 0
-#endif
 template <int SH2C, bool DQ>
 __global__ __launch_bounds__(256) void sgbm_vertical_ring_kernel(SgbmK k, const uint32_t* __restrict__ hvol,
                                                                    uint32_t* __restrict__ cvol,
@@ -617,13 +597,9 @@ __global__ __launch_bounds__(256) void sgbm_vertical_ring_kernel(SgbmK k, const 
         const uint32_t cw = pack16(cw0, cw1);
         bst32(cw, rcv, lane * 4, (uint32_t)y * rs32 * 4);
         if constexpr (DQ) {
-#if SVX_VRING_ABLATE   // A/B builds only (results invalid): the loads and stores without the path step
-            bst8(cw, rq2, lane, (uint32_t)y * rs32);
-#else
             uint32_t q;
             pk_step(cw, st, k.P1, k.P2, q);
             bst8(q_byte_pk(q), rq2, lane, (uint32_t)y * rs32);
-#endif
         } else {
             int L0, L1;
             path_step(cw0, cw1, st, k.P1, k.P2, L0, L1);
@@ -729,16 +705,6 @@ __global__ __launch_bounds__(256) void sgbm_diag_kernel(SgbmK k, const uint32_t*
 // the larger xi, i.e. the pixel visited first), so the updates need no order and no read — then disp1 (int16).
 __host__ __device__ constexpr size_t sgbm_row_lds_per_wave(int W) { return ((size_t)6 * W + 3) & ~(size_t)3; }
 
-// steps in flight in each pass (A/B builds only: -DSVX_ROW_UA=16 / -DSVX_ROW_UB=16)
-#ifndef SVX_ROW_UA
-#define SVX_ROW_UA 0
-#endif
-#ifndef SVX_ROW_UB
-#define SVX_ROW_UB 0
-#endif
-#ifndef SVX_ROW_ABLATE
-#define SVX_ROW_ABLATE 0
-#endif
 template <bool DQ>
 __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* __restrict__ cvol,
                                                          uint32_t* __restrict__ l1p, const uint32_t* __restrict__ l2vol,
@@ -747,7 +713,7 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
                                                          const uint8_t* __restrict__ q2vol,
                                                          const uint8_t* __restrict__ q3vol, int16_t* __restrict__ d16,
                                                          uint32_t* __restrict__ flags, int frames) {
-    constexpr int UA = SVX_ROW_UA > 0 && DQ ? SVX_ROW_UA : kSgPf, UB = SVX_ROW_UB > 0 && DQ ? SVX_ROW_UB : kSgPf;
+    constexpr int U = kSgPf;   // steps in flight in each pass
     extern __shared__ uint32_t rsm32[];
     const int wpb = blockDim.x >> 6, wave = wave_uniform_id();
     const int gw = blockIdx.x * wpb + wave;
@@ -776,7 +742,6 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
     // DQ: pass A stores only its own q (q0 = C - L0) and pass B forms P = sat16(4 C - (q0 + q1 + q2 + q3))
     // from the four q bytes: C is read twice, the other directions once, as 64 B a cell.
     {
-        constexpr int U = UA;
         uint32_t cc[U], ca[U], cb[U], ce[U];
         const auto load = [&](int xi, uint32_t& c, uint32_t& a, uint32_t& b, uint32_t& e) {
             xi = min(xi, n - 1);
@@ -800,14 +765,9 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
                 const int xi = x0 + u;
                 if (xi >= n) break;
                 if constexpr (DQ) {
-#if SVX_ROW_ABLATE & 1   // A/B builds only (results invalid): the loads and stores without the path step (bit 0
-                     // pass A, bit 1 pass B)
-                    bst8(cc[u], rq0, lane, (uint32_t)xi * 64);
-#else
                     uint32_t q;
                     pk_step(cc[u], sa, k.P1, k.P2, q);
                     bst8(q_byte_pk(q), rq0, lane, (uint32_t)xi * 64);
-#endif
                 } else {
                     int L0, L1;
                     path_step(lo16(cc[u]), hi16(cc[u]), sa, k.P1, k.P2, L0, L1);
@@ -829,7 +789,6 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
     // neighbours' costs are wave-uniform; step u of a group of U parks them in lane u and the
     // group's subpixel divisions and LDS updates run once, lanes 0 .. U-1 side by side, after its U steps.
     {
-        constexpr int U = UB;
         const int d0 = 2 * lane;
         uint32_t cc[U], cp[U];
         // step j visits xi = n - 1 - j (pass A's P of every cell is stored before these loads;
@@ -853,21 +812,6 @@ __global__ __launch_bounds__(256) void sgbm_row_kernel(SgbmK k, const uint32_t* 
 #pragma unroll
             for (int u = 0; u < U; ++u) load(j0 + U + u, nc[u], np[u]);
             int gkey = -1, gnum = 0, gdv = 1;   // lane u: step u's kmin (-1: no pixel written), subpixel terms
-#if SVX_ROW_ABLATE & 2
-            if constexpr (DQ) {
-                uint32_t acc = 0;
-#pragma unroll
-                for (int u = 0; u < U; ++u) acc ^= cc[u] ^ cp[u];
-                if (acc == 0x9E3779B9u) gkey = 0;   // keeps the loads
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    cc[u] = nc[u];
-                    cp[u] = np[u];
-                }
-                if (gkey >= 0) disp1[lane & 63] = 0;
-                continue;
-            }
-#endif
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int xi = n - 1 - (j0 + u);
@@ -1048,13 +992,8 @@ __device__ __forceinline__ bool cc_link(int a, int b, const SgbmK& k) {
 
 // run start of lane's pixel x (x < W) given carry = start of the previous chunk's last pixel
 __device__ __forceinline__ int cc_run_start(bool start, int x, int carry) {
-    int v = start ? x + 1 : 0;   // 0 = "no start here"
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));
-    v = max(v, __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false));
+    // 0 = "no start here": the max-scan's identity
+    const int v = wave_scan(start ? x + 1 : 0, 0, [](int a, int b) { return max(a, b); });
     return v > 0 ? v - 1 : carry;
 }
 

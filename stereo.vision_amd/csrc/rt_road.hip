@@ -341,8 +341,6 @@ int sv_batch_read_road_clean(sv_batch* b, int frame, uint8_t* img, int32_t* nzpt
 // ---------------------------------------------------------------------------
 // the obstacle stage (stereovision.py:170-189, functions.py:396-421): kernels/hull.hip
 // ---------------------------------------------------------------------------
-static_assert(kHullHostMaxH == kHullMaxH, "svx_hull_host.h and svx_hull.h disagree");
-
 int sv_road_obstacles(const uint8_t* cleaned, const uint8_t* disp, const sv_plane* plane, int H, int W,
                       const sv_camera* cam, int32_t* hull_pts, int64_t cap, uint8_t* hull_mask, uint8_t* obstacles,
                       sv_hull_info* info) {
@@ -488,10 +486,6 @@ int sv_batch_read_road_hull(sv_batch* b, int frame, int32_t* hull_pts, int64_t c
 // ---------------------------------------------------------------------------
 // the result image (stereovision.py:181-209, functions.py:390-394, :424-431): kernels/result.hip
 // ---------------------------------------------------------------------------
-static_assert(kResultHostMaxH == kResultMaxH && kResultHostMaxW == kResultMaxW &&
-                  kResultHostMaxCoord == kResultMaxCoord && kResultHostMaxVerts == kResultMaxVerts,
-              "svx_result_host.h and svx_result.h disagree");
-
 int sv_result_image(const uint8_t* bgr, const uint8_t* obstacles, const int32_t* hull_pts, int64_t n,
                     const sv_hull_info* info, int H, int W, uint8_t* out) {
     if (const char* why = result_check_args(bgr, obstacles, hull_pts, n, info, H, W, out))
@@ -581,8 +575,6 @@ int sv_batch_read_result(sv_batch* b, int frame, uint8_t* out) {
 // ---------------------------------------------------------------------------
 // the image tile (stereovision.py:216, functions.py:452-499 batchImages): kernels/tile.hip
 // ---------------------------------------------------------------------------
-static_assert(kTileHostMaxH == kTileMaxH && kTileHostMaxW == kTileMaxW, "svx_tile_host.h and svx_tile.h disagree");
-
 int sv_image_tile(const uint8_t* disparity, const uint8_t* bgr, const uint8_t* road, const uint8_t* cleaned,
                   const uint8_t* result, int H, int W, uint8_t* out) {
     if (const char* why = tile_check_args(disparity, bgr, road, cleaned, result, H, W, out))

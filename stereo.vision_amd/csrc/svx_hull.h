@@ -6,10 +6,10 @@
 
 #include "../../include/svx.h"
 #include "svx_device.h"
+#include "svx_hull_host.h"   // kHullMaxH: the limit, defined once where the host checks read it
 
 namespace svx {
 
-constexpr int kHullMaxH = 4096;       // rows of a frame the hull kernel takes (12 bytes of LDS a row)
 constexpr int kHullMaxCoord = 16383;  // |x|, |y| of launch_min_circle's points: its 64-bit centre terms hold
 constexpr int kCircleMaxPoints = 8192;   // points launch_min_circle takes: one lane, n distance tests an exchange
 

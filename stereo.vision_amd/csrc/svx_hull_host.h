@@ -10,13 +10,13 @@
 
 namespace svx {
 
-constexpr int kHullHostMaxH = 4096;   // = kHullMaxH (svx_hull.h; rt_road.hip asserts it)
+constexpr int kHullMaxH = 4096;   // rows of a frame the hull kernel takes (12 bytes of LDS a row)
 
 // nullptr when sv_road_obstacles' arguments are in range, else what is wrong with them
 inline const char* hull_check_args(const void* cleaned, const void* cam, int H, int W, const void* hull_pts,
                                    int64_t cap, const void* info) {
     if (!cleaned || !cam || !info) return "null cleaned image, camera or info";
-    if (H < 1 || H > kHullHostMaxH) return "1 <= H <= 4096";
+    if (H < 1 || H > kHullMaxH) return "1 <= H <= 4096";
     if (W < 2 || W > 4096) return "2 <= W <= 4096";
     if (cap < 0 || (cap > 0 && !hull_pts)) return "cap < 0, or cap > 0 without hull_pts";
     return nullptr;

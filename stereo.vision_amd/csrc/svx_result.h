@@ -6,13 +6,10 @@
 #include <stdint.h>
 
 #include "../../include/svx.h"
+#include "svx_result_host.h"   // kResultMaxH, kResultMaxW, kResultMaxCoord, kResultMaxVerts: the limits, defined once
+                               // where the host checks read them
 
 namespace svx {
-
-constexpr int kResultMaxH = 4096;        // rows of a frame
-constexpr int kResultMaxW = 4096;        // pixels of a row
-constexpr int kResultMaxCoord = 16383;   // |x|, |y| of a hull vertex and of the centre: the outline's terms fit 64 bits
-constexpr int kResultMaxVerts = 8192;    // vertices of a frame (the obstacle stage writes at most 2 H)
 
 // bgr, out: frames x H rows of ld3 = 3 * round_up(W, 8) bytes, frame f at + f * frame_bytes; out must not overlap
 // bgr. obst: frames x H x ceil(W / 32) words (svx_morph.h's layout, pad bits zero). pts: frame f's n int32 (x, y)

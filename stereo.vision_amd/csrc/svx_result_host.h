@@ -10,9 +10,10 @@
 
 namespace svx {
 
-constexpr int kResultHostMaxH = 4096, kResultHostMaxW = 4096;   // = kResultMaxH, kResultMaxW (svx_result.h;
-constexpr int kResultHostMaxCoord = 16383;                      //   rt_road.hip asserts them)
-constexpr int kResultHostMaxVerts = 8192;
+constexpr int kResultMaxH = 4096;        // rows of a frame
+constexpr int kResultMaxW = 4096;        // pixels of a row
+constexpr int kResultMaxCoord = 16383;   // |x|, |y| of a hull vertex and of the centre: the outline's terms fit 64 bits
+constexpr int kResultMaxVerts = 8192;    // vertices of a frame (the obstacle stage writes at most 2 H)
 
 // how often the sign of the non-zero values of d(0) .. d(n - 1) changes around the ring
 template <class F>
@@ -51,15 +52,15 @@ inline bool result_is_convex_ring(const int32_t* p, int64_t n) {
 inline const char* result_check_args(const void* bgr, const void* obstacles, const int32_t* hull_pts, int64_t n,
                                      const sv_hull_info* info, int H, int W, const void* out) {
     if (!bgr || !obstacles || !out) return "null image";
-    if (H < 1 || H > kResultHostMaxH) return "1 <= H <= 4096";
-    if (W < 2 || W > kResultHostMaxW) return "2 <= W <= 4096";
-    if (n < 0 || n > kResultHostMaxVerts || (n > 0 && !hull_pts)) return "0 <= n <= 8192, hull_pts with n > 0";
+    if (H < 1 || H > kResultMaxH) return "1 <= H <= 4096";
+    if (W < 2 || W > kResultMaxW) return "2 <= W <= 4096";
+    if (n < 0 || n > kResultMaxVerts || (n > 0 && !hull_pts)) return "0 <= n <= 8192, hull_pts with n > 0";
     for (int64_t i = 0; i < 2 * n; ++i)
-        if (hull_pts[i] < -kResultHostMaxCoord || hull_pts[i] > kResultHostMaxCoord) return "|vertex| <= 16383";
+        if (hull_pts[i] < -kResultMaxCoord || hull_pts[i] > kResultMaxCoord) return "|vertex| <= 16383";
     if (n >= 3 && !result_is_convex_ring(hull_pts, n)) return "hull_pts is no convex polygon in outline order";
     if (info && (info->valid & 2) &&
-        (info->cx < -kResultHostMaxCoord || info->cx > kResultHostMaxCoord || info->cy < -kResultHostMaxCoord ||
-         info->cy > kResultHostMaxCoord))
+        (info->cx < -kResultMaxCoord || info->cx > kResultMaxCoord || info->cy < -kResultMaxCoord ||
+         info->cy > kResultMaxCoord))
         return "|centre| <= 16383";
     return nullptr;
 }

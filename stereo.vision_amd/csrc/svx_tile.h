@@ -6,11 +6,9 @@
 #include <stdint.h>
 
 #include "../../include/svx.h"
+#include "svx_tile_host.h"   // kTileMaxH, kTileMaxW: the limits, defined once where the host checks read them
 
 namespace svx {
-
-constexpr int kTileMaxH = 4096;   // rows of a frame
-constexpr int kTileMaxW = 4096;   // pixels of a row
 
 // A picture of `frames` frames: frame f at + f * frame (bytes for a u8 picture, words for a bitmap), its rows ld
 // apart (bytes or words).

@@ -8,14 +8,14 @@
 
 namespace svx {
 
-constexpr int kTileHostMaxH = 4096, kTileHostMaxW = 4096;   // = kTileMaxH, kTileMaxW (svx_tile.h; rt_road.hip
-                                                            //   asserts them)
+constexpr int kTileMaxH = 4096;   // rows of a frame
+constexpr int kTileMaxW = 4096;   // pixels of a row
 
 // nullptr when a frame of H x W has a tile, else what is wrong with the shape: the quadrants of the stack meet on
 // output-pixel boundaries only when H and W are multiples of 4
 inline const char* tile_check_shape(int H, int W) {
-    if (H < 4 || H > kTileHostMaxH || H % 4) return "H a multiple of 4, 4 <= H <= 4096";
-    if (W < 4 || W > kTileHostMaxW || W % 4) return "W a multiple of 4, 4 <= W <= 4096";
+    if (H < 4 || H > kTileMaxH || H % 4) return "H a multiple of 4, 4 <= H <= 4096";
+    if (W < 4 || W > kTileMaxW || W % 4) return "W a multiple of 4, 4 <= W <= 4096";
     return nullptr;
 }
 

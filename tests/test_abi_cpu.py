@@ -60,6 +60,30 @@ def test_release_library_reads_no_knobs():
         assert b"SVX_ABLATE" in dblob and b"SVX_RANSAC_ABLATE" in dblob
 
 
+def test_sources_have_no_compile_time_selectors():
+    """A code path is in the release library or in the diagnostic one (-DSVX_DIAG: svx_knob / ablated()) and
+    nowhere else: the only preprocessor conditionals under csrc test SVX_DIAG, or SVX_SRCID_K1 (the source ids the
+    Makefile passes to runtime.hip). A path behind any other macro is one that no build compiles."""
+    csrc = os.path.join(REPO, "stereo.vision_amd", "csrc")
+    allowed = {"SVX_DIAG", "SVX_SRCID_K1"}
+    found, bad = 0, []
+    for root, dirs, files in os.walk(csrc):
+        dirs[:] = [d for d in dirs if not d.startswith("_obj")]
+        for name in files:
+            if not name.endswith((".h", ".hip", ".cpp")):
+                continue
+            path = os.path.join(root, name)
+            text = open(path).read().replace("\\\n", " ")
+            for m in re.finditer(r"^[ \t]*#[ \t]*(if|ifdef|ifndef|elif)\b(.*)$", text, re.M):
+                found += 1
+                expr = re.sub(r"//.*|/\*.*?\*/", "", m.group(2))
+                names = set(re.findall(r"[A-Za-z_]\w*", expr)) - {"defined"}
+                if not names or not names <= allowed:
+                    bad.append(f"{os.path.relpath(path, csrc)}: {m.group(0).strip()}")
+    assert found > 0, "no conditional found: the walk saw no source"
+    assert not bad, bad
+
+
 def test_diagnostic_library_loads_with_its_probes():
     """The diagnostic build loads (every symbol it uses resolves) and exports the evaluation's phase clocks
     (tools/_probe_eval_phases.py); the release build does not export them."""
