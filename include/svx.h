@@ -226,9 +226,12 @@ int sv_result_image(const uint8_t* bgr, const uint8_t* obstacles, const int32_t*
  * quadrants then meet on output-pixel boundaries (H / 4, W / 4) and no output pixel mixes two pictures. A road or
  * cleaned picture of 0 and 255 gives quadrant bytes of {0, 64, 128, 191, 255}, by the number of its four samples
  * that are set; other bytes are averaged as they are.
- * Not built: tiles of frames whose H or W is no multiple of 4, the 390 x 889 cropped batch among them. There the
- * reference first resizes its cropped pictures to 544 x 1024 with cv2.resize's general-scale bilinear filter, and
- * that resize is not restated here. Tiles of one to four pictures are not built either.
+ * Not built by this entry point: tiles of frames whose H or W is no multiple of 4, pictures of other shapes than
+ * the frame's (the 390 x 889 cropped disparity, which the reference first resizes to 544 x 1024 with cv2.resize's
+ * general-scale bilinear filter) and lists of one to four pictures. Those go through the general-scale resize
+ * below: sv_resize_linear_u8 for a picture, sv_images_tile for a list, sv_batch_resize_disp for a batch's
+ * disparity. The whole tile of a cropped batch on the device is not built: that batch runs its road chain on the
+ * 390 x 889 grid, while the reference in that mode cleans, hulls and draws 544 x 1024 pictures.
  * Parity with OpenCV is unpinned: cv2 is absent here. The argument for equality: INTER_LINEAR at scale 4 samples at
  * 4 dx + 1.5, so both weights are 1/2 = 1024 / 2048 in its 11-bit fixed point, and at scale 2 it is the 2 x 2 area
  * mean; all four weights are exactly 1/4, so any fixed-point or float implementation that rounds to nearest with
@@ -240,6 +243,48 @@ int sv_result_image(const uint8_t* bgr, const uint8_t* obstacles, const int32_t*
  * multiple of 4 in 4 .. 4096. */
 int sv_image_tile(const uint8_t* disparity, const uint8_t* bgr, const uint8_t* road, const uint8_t* cleaned,
                   const uint8_t* result, int H, int W, uint8_t* out);
+
+/* ---- general-scale bilinear resize (functions.py:452-454 resizeImage, :456-501 batchImages) ---- */
+
+/* cv2.resize's 8-bit INTER_LINEAR path at any scale, as tests/tile_numpy.py restates it (resize_linear_u8): a
+ * float32 source coordinate, int16 coefficients of 11-bit fixed point rounded half to even, an int32 horizontal
+ * pass, the vertical pass's two >> 16 products and a final + 2 >> 2. Parity with OpenCV itself is unpinned: cv2 is
+ * absent here; every result is bit for bit the restatement's.
+ * The coefficient table of one axis, dn destination indices over sn source ones (host code, no device): with
+ * scale = 1.0 / ((double)dn / sn) and f = (float)((dx + 0.5) * scale - 0.5), s = floor(f), f -= s; s < 0 gives
+ * s = 0, f = 0 and s >= sn - 1 gives s = sn - 1, f = 0; s0[dx] = s, s1[dx] = min(s + 1, sn - 1),
+ * c0[dx] = rint((1.f - f) * 2048.f), c1[dx] = rint(f * 2048.f), both half to even in float32. Fills dn entries of
+ * each table. SV_E_ARG for a NULL table or dn or sn outside 1 .. 8192. The device reads these tables as they are. */
+int sv_resize_coefficients(int dn, int sn, int32_t* s0, int32_t* s1, int16_t* c0, int16_t* c1);
+/* n packed images of sh x sw x channels in, n packed images of dh x dw x channels out, one launch, synchronous:
+ * cv2.resize(src[i], (dw, dh)). channels is 1 or 3; source dimensions 1 .. 8192, destination dimensions 1 .. 4096.
+ * SV_E_ARG for a NULL pointer, dst overlapping src, n < 1 or a dimension out of range. */
+int sv_resize_linear_u8(const uint8_t* src, int n, int sh, int sw, int channels, uint8_t* dst, int dh, int dw);
+
+/* One picture of a batchImages list: h x w x channels u8, packed; channels 1 (grey) or 3 (BGR). */
+typedef struct {
+    const uint8_t* data;
+    int h, w, channels;
+} sv_picture;
+/* batchImages(imgList, (H, W)) (functions.py:456-501) for count = 1 .. 5 pictures of any shapes within 1 .. 4096,
+ * composed on the device as the reference composes it: every picture is resized to H x W by the resize above (one
+ * already of that size too: the filter is then the identity), a grey one becomes BGR by repeating its byte, the
+ * stack is built in device memory and resized by the same kernel:
+ *   count 1: the resized picture                                                          H x W x 3
+ *   count 2: resize(hstack(0, 1), fx = fy = 0.5)                                          H / 2 x W x 3, H even
+ *   count 3: resize(vstack(hstack(0, 1), hstack(2, 2)), 0.5)                              H x W x 3
+ *   count 4: resize(vstack(hstack(0, 1), hstack(2, 3)), 0.5)                              H x W x 3
+ *   count 5: hstack(resize(that stack, 0.25), resize(picture 4, 0.5))                     H / 2 x W x 3, H, W even
+ * H and W need not be multiples of 4: an output pixel of the left part may mix two pictures, and it is right
+ * because the stack really exists. The fx / fy resize is built only where the stack's size is an exact multiple of
+ * the scale, hence the even H (count 2) and the even H and W (count 5): elsewhere OpenCV takes its scale from fx
+ * and not from the rounded dsize, and its scale-2 area path has a tail that is restated nowhere. For the list
+ * sv_image_tile takes the two entry points give the same bytes.
+ * sv_images_tile_shape: the output's rows and columns. sv_images_tile: out of that shape x 3, overlapping no
+ * picture; one host call, synchronous. SV_E_ARG for a NULL pointer, an overlap, count outside 1 .. 5, channels
+ * other than 1 or 3, a dimension out of range or an odd H or W excluded above. */
+int sv_images_tile_shape(int count, int H, int W, int* oh, int* ow);
+int sv_images_tile(const sv_picture* pics, int count, int H, int W, uint8_t* out);
 
 /* ---- the stages a2-a6 one by one (the stage drop-ins) ---------------------- */
 
@@ -470,6 +515,17 @@ int sv_batch_tile(sv_batch* b, int sync);
 int sv_batch_read_tile(sv_batch* b, int frame, uint8_t* out);
 /* ms of the last sv_batch_tile from HIP events on the batch stream. Synchronises the batch stream. */
 int sv_batch_tile_ms(sv_batch* b, float* ms);
+/* The cleaned disparity of every frame (what sv_batch_read_disp returns) at a display size, on the device:
+ * cv2.resize(disp, (dw, dh)) by sv_resize_linear_u8's kernel in one launch over the resident frames, read at the
+ * batch's row stride, into a buffer of its own (frames x dh x dw bytes, packed; allocated by the first call). For a
+ * crop_disparity batch of 390 x 889 and (544, 1024) it is the Disparity picture of that mode's tile. Whatever
+ * replaces the cleaned disparity (an upload, synthetic frames, SGBM, a pre-pass) makes it stale: reads and _ms then
+ * give SV_E_STATE, as before the first call. SV_E_ARG for dh or dw outside 1 .. 4096 or frames beyond 8192 x 8192. */
+int sv_batch_resize_disp(sv_batch* b, int dh, int dw, int sync);
+/* One frame's resized disparity, dh x dw u8. */
+int sv_batch_read_resized_disp(sv_batch* b, int frame, uint8_t* out);
+/* ms of the last sv_batch_resize_disp from HIP events on the batch stream. Synchronises the batch stream. */
+int sv_batch_resize_disp_ms(sv_batch* b, float* ms);
 
 /* Batched RANSAC (stereovision.py:84-94 for every frame):
  * maskpoints = the fp64 step-2 projection of the batch's disparity under the

@@ -265,7 +265,7 @@ int sv_batch_destroy(sv_batch* b) {
                       &b->carmask, &b->road, &b->rmap, &b->nz, &b->nzcount, &b->mpts, &b->mpk, &b->rres, &b->rtab, &b->rtrace, &b->fplanes, &b->dplane, &b->abc,
                       &b->pairL, &b->pairR, &b->rsidx, &b->rtri, &b->bgrL, &b->bgrR,
                       &b->glut, &b->ghist, &b->sgflags, &b->prev0buf, &b->rdbuf, &b->rbits, &b->roff, &b->raw, &b->rmask, &b->cpack,
-                      &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff, &b->hbuf, &b->rimg, &b->timg})
+                      &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff, &b->hbuf, &b->rimg, &b->timg, &b->rdisp, &b->rdtab})
         x->release();
     if (b->hcnt) (void)hipHostFree(b->hcnt);
     if (b->cnt_ev) (void)hipEventDestroy(b->cnt_ev);
@@ -273,6 +273,8 @@ int sv_batch_destroy(sv_batch* b) {
     for (auto& ev : b->ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->road_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : b->rd_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->pool) (void)hipEventDestroy(ev);
     for (auto& ev : b->sync_ev) (void)hipEventDestroy(ev);
@@ -313,6 +315,7 @@ int sv_batch_synth(sv_batch* b, int64_t first_frame_id) {
     if (!b) return fail(SV_E_ARG, "null batch");
     if (b->Wu != b->W) return fail(SV_E_ARG, "synthetic frames need W %% 8 == 0 (W=%d)", b->Wu);
     HIP_TRY(hipSetDevice(b->device));
+    b->rdisp_fresh = false;
     HIP_TRY(launch_synth(b->kp, input_disp(b), b->with_bgr ? b->bgr.as<uint8_t>() : nullptr,
                          b->frames, first_frame_id, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -325,6 +328,7 @@ int sv_batch_upload(sv_batch* b, int frame, const uint8_t* disp, const uint8_t* 
     HIP_TRY(hipSetDevice(b->device));
     const size_t px = (size_t)b->H * b->W;
     uint8_t* dd = input_disp(b) + px * frame;
+    b->rdisp_fresh = false;
     if (b->Wu == b->W) {
         HIP_TRY(hipMemcpyAsync(dd, disp, px, hipMemcpyHostToDevice, b->stream));
     } else {   // rows at the padded stride, pad columns zero (outside every grid)

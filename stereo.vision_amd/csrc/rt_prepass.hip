@@ -9,6 +9,7 @@ int batch_prepass_impl(sv_batch* b, int option, const uint8_t* dprev0) {
     uint8_t* disp = b->disp.as<uint8_t>();
     const uint8_t* in = input_disp(b);   // keep_input: the raw frames, read here and never written
     const int64_t px = (int64_t)b->H * b->W;
+    b->rdisp_fresh = false;   // new cleaned frames: a resized disparity is not theirs
     if (option == 1) {
         HIP_TRY(launch_fill_prev(in, disp, masked, mff, dprev0, b->frames, px, b->stream));
     } else {

@@ -388,6 +388,7 @@ int sv_batch_sgbm(sv_batch* b, const sv_sgbm_params* prm, int max_disparity, int
         if (int rc = sgbm_place(b, k, chunk, b->pairL.as<uint8_t>(), b->pairR.as<uint8_t>())) return rc;
     }
     HIP_TRY(b->sg.ensure(k, chunk));
+    b->rdisp_fresh = false;
     int t0, t1;
     HIP_TRY(hipEventRecord(b->ev[4], b->stream));
     HIP_TRY(b->timed_event(&t0));

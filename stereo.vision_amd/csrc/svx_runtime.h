@@ -144,6 +144,7 @@ struct Device {
     DevBuf hull;                      // sv_road_obstacles: bitmaps, vertices and info (HullLayout)
     DevBuf res;                       // sv_result_image: image, obstacle bitmap, vertices and info (ResultLayout)
     DevBuf tile;                      // sv_image_tile: the staged result image and the tile (TileLayout)
+    DevBuf rsz;                       // sv_resize_linear_u8, sv_images_tile: tables, staged pictures, stack, output
     DevBuf sg_l, sg_r, sg_out, sg_filt, sg_hist;   // host-frame SGBM / grey drop-ins
     SgbmBufs sg;
     Tables tables;
@@ -239,6 +240,13 @@ struct sv_batch {
     DevBuf rimg;
     // the image tile (sv_batch_tile): frames x H / 2 rows of 3 Wu bytes, packed; made on first use
     DevBuf timg;
+    // the cleaned disparity at a display size (sv_batch_resize_disp): frames x rd_h x rd_w bytes, packed, and the
+    // coefficient tables of that size (svx_resize_host.h); made on first use. rdisp_fresh: it is the resize of what
+    // `disp` holds now: whatever writes the batch's frames or cleans them again clears it.
+    DevBuf rdisp, rdtab;
+    int rd_h = 0, rd_w = 0, rdtab_h = 0, rdtab_w = 0;
+    bool rdisp_fresh = false;
+    hipEvent_t rd_ev[2] = {nullptr, nullptr};
     DevBuf mpts, rres;          // one frame's maskpoints as fp64 (read-back scratch); counts + batched RANSAC results
     DevBuf prev0buf, rdbuf;     // the host prev0 of sv_batch_prepass; sv_batch_read_disp's masked frame (batch-owned:
                                 // the device-wide drop-in scratch is used on other streams)

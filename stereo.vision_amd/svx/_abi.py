@@ -40,6 +40,11 @@ class HullInfo(ctypes.Structure):
                 ("tipx", ctypes.c_int64), ("tipy", ctypes.c_int64)]
 
 
+class Picture(ctypes.Structure):
+    """sv_picture (include/svx.h)."""
+    _fields_ = [("data", ctypes.c_void_p), ("h", ctypes.c_int), ("w", ctypes.c_int), ("channels", ctypes.c_int)]
+
+
 P = ctypes.c_void_p
 I = ctypes.c_int
 I64 = ctypes.c_int64
@@ -93,6 +98,13 @@ SIGNATURES = {
     "sv_batch_tile": [P, I],
     "sv_batch_read_tile": [P, I, P],
     "sv_batch_tile_ms": [P, PF],
+    "sv_resize_coefficients": [I, I, P, P, P, P],
+    "sv_resize_linear_u8": [P, I, I, I, I, P, I, I],
+    "sv_images_tile_shape": [I, I, I, ctypes.POINTER(I), ctypes.POINTER(I)],
+    "sv_images_tile": [ctypes.POINTER(Picture), I, I, I, P],
+    "sv_batch_resize_disp": [P, I, I, I],
+    "sv_batch_read_resized_disp": [P, I, P],
+    "sv_batch_resize_disp_ms": [P, PF],
     "sv_point_errors": [P, I64, I64, P, P],
     "sv_hue_histogram": [P, I64, I64, P, P, P],
     "sv_select_less": [P, I64, D, P, PI64],

@@ -347,6 +347,26 @@ class Batch:
         _abi.call("sv_batch_read_tile", self._h, frame, _abi.ptr(out))
         return out
 
+    def resize_disp(self, size, sync=True):
+        """The cleaned disparity of every frame (read_disp) at size = (dh, dw), on the device: cv2.resize's 8-bit
+        bilinear path in one launch over the resident frames (sv_batch_resize_disp). For a 390 x 889 cropped batch
+        and (544, 1024) it is the Disparity picture of that mode's tile. New frames or a new pre-pass make it stale."""
+        dh, dw = (int(v) for v in size)
+        _abi.call("sv_batch_resize_disp", self._h, dh, dw, int(sync))
+        self._resized = (dh, dw)
+
+    def resize_disp_ms(self):
+        """ms of the last resize_disp(), from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_resize_disp_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
+    def read_resized_disp(self, frame):
+        """One frame's resized disparity, (dh, dw) uint8."""
+        out = np.empty(getattr(self, "_resized", None) or (1, 1), np.uint8)
+        _abi.call("sv_batch_read_resized_disp", self._h, frame, _abi.ptr(out))
+        return out
+
     def ransac(self, seed_base, trials, k=600, first_frame=0, camera=None, sync=True):
         """RANSAC(maskpoints, trials) of every frame on the device (stereovision.py:84-94), frame F
         drawing what CPython draws after random.seed(seed_base + first_frame + F)."""

@@ -43,6 +43,10 @@ reference:
 * ``batchImages(imgList, size)`` (functions.py:456-501): the five-picture tile of
   stereovision.py:216 on the GPU (``image_tile`` is its array form); other lists go to the
   function it replaced. Installed only with ``install(.., tiles=True)``.
+* ``resizeImage(image, height, width)`` and ``batchImages`` for any list of one to five
+  pictures (functions.py:452-501): cv2.resize's 8-bit bilinear path at any scale on the GPU
+  (``resize_linear``, ``images_tile`` are the array forms). Installed only with
+  ``install(.., resize=True)``.
 * disparity pre-pass (functions.py:141-172): ``fillDisparity`` (new array, or
   the input itself when there is no previous frame), ``fillAltDisparity`` (in
   place, returns its argument), ``maskDisparity`` (new array; the mask is the
@@ -414,6 +418,121 @@ def batchImages(imgList, size):  # noqa: N802,N803
     return orig(imgList, size)
 
 
+# ---------------------------------------------------------------------------
+# general-scale bilinear resize (functions.py:452-454, :456-501)
+# ---------------------------------------------------------------------------
+RESIZE_MAX_SRC, RESIZE_MAX_DST = 8192, 4096   # include/svx.h, sv_resize_linear_u8
+
+
+def resize_linear(img, size):
+    """cv2.resize(img, (dw, dh)) of a uint8 image on the GPU, size = (dw, dh) as cv2 takes it: OpenCV's 8-bit
+    INTER_LINEAR path at any scale (include/svx.h, sv_resize_linear_u8; unpinned against cv2 itself). img: (H, W)
+    or (H, W, 3); or a stack (n, H, W, 3), or (n, H, W) whose W is not 3, resized in one launch. Source dimensions
+    1..8192, destination dimensions 1..4096."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8:
+        raise TypeError(f"image must be uint8, got {a.dtype}")
+    dw, dh = (int(v) for v in size)
+    if a.ndim == 2:
+        lead, (sh, sw), ch = (), a.shape, 1
+    elif a.ndim == 3 and a.shape[2] == 3:
+        lead, (sh, sw), ch = (), a.shape[:2], 3
+    elif a.ndim == 3:
+        lead, (sh, sw), ch = a.shape[:1], a.shape[1:], 1
+    elif a.ndim == 4 and a.shape[3] == 3:
+        lead, (sh, sw), ch = a.shape[:1], a.shape[1:3], 3
+    else:
+        raise ValueError(f"image must be (H, W), (H, W, 3), (n, H, W) or (n, H, W, 3), got shape {a.shape}")
+    a = np.ascontiguousarray(a)
+    out = np.empty(lead + (max(dh, 0), max(dw, 0)) + ((3,) if ch == 3 else ()), np.uint8)
+    _abi.call("sv_resize_linear_u8", _abi.ptr(a), lead[0] if lead else 1, sh, sw, ch, _abi.ptr(out), dh, dw)
+    return out
+
+
+def _list_images(imgList):  # noqa: N803
+    """The arrays of a batchImages list: [(name, image)] pairs or plain arrays."""
+    return [np.asarray(i[1] if isinstance(i, (tuple, list)) else i) for i in imgList]
+
+
+def _images_tile_shape(imgs, size):
+    """The (rows, columns) of batchImages(imgs, size) where the device builds it (include/svx.h, sv_images_tile), else
+    None: a dtype other than uint8, other than 1..5 pictures, an odd H or W the final resize excludes, or a dimension
+    beyond the limits. Host arithmetic only."""
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        return None
+    n = len(imgs)
+    if not (1 <= n <= 5 and 1 <= H <= RESIZE_MAX_DST and 1 <= W <= RESIZE_MAX_DST):
+        return None
+    if (n in (2, 5) and H % 2) or (n == 5 and W % 2):
+        return None
+    for a in imgs:
+        if a.dtype != np.uint8 or not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+            return None
+        if not (1 <= a.shape[0] <= RESIZE_MAX_DST and 1 <= a.shape[1] <= RESIZE_MAX_DST):
+            return None
+    return (H // 2 if n in (2, 5) else H), W
+
+
+def images_tile(imgList, size):  # noqa: N803
+    """batchImages(imgList, size) (functions.py:456-501) on the GPU for one to five pictures, size = (H, W): a list of
+    (name, image) pairs or of arrays, each (h, w) or (h, w, 3) uint8 of any shape within 1..4096. Every picture is
+    resized to `size`, grey becomes BGR, the stack is built and resized on the device as the reference composes it
+    (include/svx.h, sv_images_tile). H even for two pictures, H and W even for five."""
+    imgs = [np.ascontiguousarray(a) for a in _list_images(imgList)]
+    for a in imgs:
+        if a.dtype != np.uint8:
+            raise TypeError(f"images must be uint8, got {a.dtype}")
+        if not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+            raise ValueError(f"images must be (h, w) or (h, w, 3), got shape {a.shape}")
+    H, W = (int(v) for v in size)
+    n = len(imgs)
+    pics = (_abi.Picture * max(n, 1))()
+    for k, a in enumerate(imgs[:len(pics)]):
+        pics[k] = _abi.Picture(a.ctypes.data, a.shape[0], a.shape[1], 3 if a.ndim == 3 else 1)
+    oh, ow = ctypes.c_int(0), ctypes.c_int(0)
+    _abi.call("sv_images_tile_shape", n, H, W, ctypes.byref(oh), ctypes.byref(ow))
+    out = np.empty((oh.value, ow.value, 3), np.uint8)
+    _abi.call("sv_images_tile", pics, n, H, W, _abi.ptr(out))
+    return out
+
+
+def resizeImage(image, height, width):  # noqa: N802
+    """functions.py:452-454, cv2.resize(image, (width, height)), on the GPU (resize_linear). An image the kernel does
+    not take (not uint8, not (H, W) or (H, W, 3), a dimension beyond the limits) goes to the function install()
+    replaced; without one, SvxError. Installed only with install(.., resize=True)."""
+    a = np.asarray(image)
+    ok = a.dtype == np.uint8 and (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)) and \
+        all(1 <= v <= RESIZE_MAX_SRC for v in a.shape[:2]) and \
+        1 <= int(height) <= RESIZE_MAX_DST and 1 <= int(width) <= RESIZE_MAX_DST
+    if ok:
+        return resize_linear(a, (width, height))
+    orig = _saved.get("resizeImage", _ABSENT)
+    if orig is _ABSENT or orig is None:
+        raise _abi.SvxError("resizeImage: only uint8 (H, W) or (H, W, 3) images within the limits are resized on the "
+                            "device, and no function was replaced to take this one")
+    return orig(image, height, width)
+
+
+def batch_images(imgList, size):  # noqa: N803
+    """functions.py:456-501 for any list the device takes (images_tile): one to five uint8 pictures of any shapes.
+    A list it cannot take (a dtype other than uint8, no or more than five pictures, an odd H or W that the final
+    resize excludes, a dimension beyond the limits) goes to the function install() replaced, which needs cv2 as
+    before; without one, SvxError. This is what install(.., resize=True) puts in batchImages' place."""
+    try:
+        imgs = _list_images(imgList)
+    except (TypeError, ValueError, IndexError):
+        imgs = None
+    if imgs is not None and _images_tile_shape(imgs, size) is not None:
+        return images_tile(imgs, size)
+    orig = _saved.get("batchImages", _ABSENT)
+    if orig is _ABSENT or orig is None:
+        raise _abi.SvxError("batchImages: one to five uint8 pictures within 1..4096 (H even for two, H and W even for "
+                            "five) are built on the device, and no function was replaced to take this list")
+    return orig(imgList, size)
+
+
 def getCenterPoint(points):  # noqa: N802
     """functions.py:418-421 with the exact circle: (int(x), int(y)) of the centre of the minimum enclosing circle of
     any (n, 1, 2) or (n, 2) integer points (|coordinate| <= 16383, at most 8192 distinct ones), computed in integers on the GPU. The reference's
@@ -463,13 +582,18 @@ HULL = ("getCenterPoint",)
 # batchImages (functions.py:456-501) restates cv2.resize at the two scales stereovision.py:216 uses (exact quarter
 # weights, include/svx.h): unpinned as well, installed only with install(.., tiles=True).
 TILES = ("batchImages",)
+# resizeImage and batchImages (functions.py:452-501) over cv2.resize's 8-bit bilinear path at any scale (include/svx.h,
+# sv_resize_linear_u8, sv_images_tile): unpinned likewise, installed only with install(.., resize=True). With
+# tiles=True as well, this group decides batchImages.
+RESIZE = ("resizeImage", "batchImages")
+_RESIZE_IMPL = {"resizeImage": "resizeImage", "batchImages": "batch_images"}
 ALIASES = {"project_disparity_to_3d": "projectDisparityTo3d",
            "project_3D_points_to_2D": "project3DPointsTo2DImagePoints"}
 _saved = {}
 _ABSENT = object()
 
 
-def install(functions_module, unpinned=False, morphology=False, hull=False, tiles=False):
+def install(functions_module, unpinned=False, morphology=False, hull=False, tiles=False, resize=False):
     """Patch the reference's `functions` module in place (stereovision.py resolves
     f.<name> at call time, so performStereoVision picks the GPU path up).
 
@@ -482,16 +606,19 @@ def install(functions_module, unpinned=False, morphology=False, hull=False, tile
     pixel walk, with the module's road_threshold_mask), a restatement of cv2 calls as well;
     hull=True also replaces getCenterPoint (HULL) by the exact circle's centre; tiles=True
     also replaces batchImages (TILES): the five-picture tile on the device, any other list
-    handed on to the module's own function."""
+    handed on to the module's own function; resize=True replaces resizeImage and batchImages
+    (RESIZE) by the general-scale resize: any list of one to five uint8 pictures is composed on
+    the device, and it decides batchImages when tiles=True is given too."""
     global _module
     _abi.lib()  # fail loudly now if libsvx is missing
     _module = functions_module
     names = PINNED + (UNPINNED if unpinned else ()) + (MORPHOLOGY if morphology else ()) + \
-        (HULL if hull else ()) + (TILES if tiles else ()) + tuple(ALIASES)
+        (HULL if hull else ()) + (TILES if tiles else ()) + (RESIZE if resize else ()) + tuple(ALIASES)
     for name in names:
         if name not in _saved:
             _saved[name] = getattr(functions_module, name, _ABSENT)
-        setattr(functions_module, name, globals()[ALIASES.get(name, name)])
+        impl = _RESIZE_IMPL[name] if resize and name in RESIZE else ALIASES.get(name, name)
+        setattr(functions_module, name, globals()[impl])
     return functions_module
 
 
