@@ -246,6 +246,30 @@ int sv_image_tile(const uint8_t* disparity, const uint8_t* bgr, const uint8_t* r
 
 /* ---- general-scale bilinear resize (functions.py:452-454 resizeImage, :456-501 batchImages) ---- */
 
+/* ---- the MJPG recording (loop.py:49-54,82-89: cv2.VideoWriter(name, MJPG, 8, (1024, 272)), write(image),
+ * release()) ---- */
+/* The picture the loop records leaves the device as a baseline JPEG stream, made on the GPU (kernels/jpeg.hip;
+ * svx.video.VideoWriter puts the streams into the AVI). The stream of a BGR u8 picture of h x w, 1 .. 4096 each way
+ * (tests/jpeg_numpy.py restates it): SOI, JFIF APP0, DQT x 2 (Annex K.1 / K.2 under the IJG quality
+ * rule), SOF0 (Y 2 x 2, Cb and Cr 1 x 1), DHT x 4 (Annex K.3 - K.6), DRI = ceil(w / 16), SOS, one interleaved scan
+ * with RSTn between the MCU rows, EOI. Colour, the 2 x 2 chroma means, the slow-integer DCT, the quantiser and the
+ * entropy coder are libjpeg's, so the scan's bytes equal libjpeg's at the same quality with 4:2:0 and a restart
+ * interval of one MCU row (checked against Pillow / libjpeg-turbo on the test list). Parity with OpenCV's own MJPG
+ * encoder, a different one inside cv2, is unpinned.
+ *
+ * sv_jpeg_bound (loop.py:49-54,82-89): a capacity no stream of this definition exceeds: 640 bytes for the header
+ * (it is 629), and for each of the ceil(h / 16) restart intervals its ceil(w / 16) MCUs at their worst code lengths
+ * - 4 (20 + 63 * 26) + 2 (22 + 63 * 26) bits = 1244 bytes an MCU: a DC code with its bits is at most 9 + 11 bits
+ * (luma) or 11 + 11 (chroma), an AC one 16 + 10 - every byte of them stuffed (x 2), and 2 bytes of RSTn or EOI.
+ * 0 for dimensions outside 1 .. 4096. */
+int64_t sv_jpeg_bound(int h, int w);
+/* One host picture (loop.py:49-54,82-89, VideoWriter.write): rows ld >= 3 w bytes apart, quality 1 .. 100 (75 is
+ * the writer's default). *size = the stream's length. SV_E_ARG for nulls, dimensions outside 1 .. 4096, quality
+ * outside 1 .. 100, ld < 3 w or cap < 0. A stream longer than cap: SV_E_CAP with *size = the length it needs;
+ * nothing is written to out then (and never past out + cap). */
+int sv_jpeg_encode(const uint8_t* bgr, int h, int w, int64_t ld, int quality, uint8_t* out, int64_t cap,
+                   int64_t* size);
+
 /* cv2.resize's 8-bit INTER_LINEAR path at any scale, as tests/tile_numpy.py restates it (resize_linear_u8): a
  * float32 source coordinate, int16 coefficients of 11-bit fixed point rounded half to even, an int32 horizontal
  * pass, the vertical pass's two >> 16 products and a final + 2 >> 2. Parity with OpenCV itself is unpinned: cv2 is
@@ -515,6 +539,29 @@ int sv_batch_tile(sv_batch* b, int sync);
 int sv_batch_read_tile(sv_batch* b, int frame, uint8_t* out);
 /* ms of the last sv_batch_tile from HIP events on the batch stream. Synchronises the batch stream. */
 int sv_batch_tile_ms(sv_batch* b, float* ms);
+/* The JPEG stream (sv_jpeg_encode; loop.py:49-54,82-89) of every frame's tile, on the device, each into a slot of
+ * cap_per_frame bytes (0: half the raw tile, at least 2048; noise at quality 75 takes 0.20 of the raw bytes, at 100
+ * 0.66). The coefficients go through a scratch of 3 B a pixel in chunks of frames sized from the free memory. A frame
+ * whose stream is longer than the slot is flagged in its size and not written; the call still succeeds. SV_E_STATE
+ * without a current tile (sv_batch_tile); whatever invalidates the tile invalidates the streams. SV_E_ARG for a
+ * quality outside 1 .. 100 or a capacity outside 0 .. 2^31 - 1. */
+int sv_batch_jpeg(sv_batch* b, int quality, int64_t cap_per_frame, int sync);
+/* The lengths of the streams of sv_batch_jpeg (loop.py:49-54,82-89), frames x int32; negative: the frame
+ * overflowed its slot, minus the length it needs. */
+int sv_batch_jpeg_sizes(sv_batch* b, int32_t* out);
+/* One frame's stream (loop.py:49-54,82-89: what VideoWriter.write would encode of that frame's tile). *size = its
+ * length; SV_E_CAP when the frame overflowed its slot or cap is smaller than the stream (*size = what it needs). */
+int sv_batch_read_jpeg(sv_batch* b, int frame, uint8_t* out, int64_t cap, int64_t* size);
+/* The batch's streams back to back in frame order (loop.py:49-54,82-89, a batch's worth of write calls): an
+ * exclusive scan of the sizes and one copy kernel on the device, then sv_batch_read_jpeg_packed copies exactly their
+ * bytes in one transfer. offsets: frames x int64, each frame's start (a frame that overflowed its slot contributes
+ * nothing: its offset equals the next one's); *total = the bytes of the run. SV_E_STATE before sv_batch_jpeg_pack of
+ * the current streams; SV_E_CAP (with *total set) when cap < total. */
+int sv_batch_jpeg_pack(sv_batch* b, int sync);
+int sv_batch_read_jpeg_packed(sv_batch* b, uint8_t* out, int64_t cap, int64_t* offsets, int64_t* total);
+/* ms of the last sv_batch_jpeg (loop.py:49-54,82-89's encode) from HIP events on the batch stream. Synchronises
+ * the batch stream. */
+int sv_batch_jpeg_ms(sv_batch* b, float* ms);
 /* The cleaned disparity of every frame (what sv_batch_read_disp returns) at a display size, on the device:
  * cv2.resize(disp, (dw, dh)) by sv_resize_linear_u8's kernel in one launch over the resident frames, read at the
  * batch's row stride, into a buffer of its own (frames x dh x dw bytes, packed; allocated by the first call). For a
@@ -651,7 +698,10 @@ typedef struct {
                             batch sv_loop_batch returns), 5 all of 4 + the result image
                             (sv_batch_result; sv_batch_read_result), 6 all of 5 + the image tile
                             (sv_batch_tile; sv_batch_read_tile; H and W multiples of 4, checked by
-                            sv_loop_create), inside the timeline's "road" stage */
+                            sv_loop_create), 7 "video": all of 6 + the tiles' JPEG streams and their pack
+                            (loop.py:49-54,82-89; sv_batch_jpeg, sv_batch_jpeg_pack; quality and slot:
+                            sv_loop_jpeg; sv_batch_read_jpeg, sv_batch_read_jpeg_packed), inside the timeline's
+                            "road" stage */
 } sv_loop_params;
 typedef struct sv_loop sv_loop;
 /* carmask: the grey H x W mask of maskDisparity (functions.py:35, :169-172), NULL for none. */
@@ -663,6 +713,10 @@ int sv_loop_destroy(sv_loop* L);
  * (sv_batch_read_road_clean). mask: the H x W road_threshold_mask for every slot, NULL = all ones (the default);
  * it applies to the batches whose road stage is enqueued after the call. */
 int sv_loop_road_mask(sv_loop* L, const uint8_t* mask);
+/* road = 7 (loop.py:49-54,82-89): the quality (1 .. 100; 75 unless set) and the slot capacity (0 = the default of
+ * sv_batch_jpeg) of every batch's streams. SV_E_STATE after the first sv_loop_submit. sv_loop_params keeps its
+ * layout. */
+int sv_loop_jpeg(sv_loop* L, int quality, int64_t cap_per_frame);
 /* The batch the next sv_loop_submit runs (waits on the host until its slot's previous batch is done): with
  * source 0 the caller uploads its frames (or runs sv_batch_sgbm on it) before submitting. */
 int sv_loop_acquire(sv_loop* L, sv_batch** out);

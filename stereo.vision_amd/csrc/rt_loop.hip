@@ -32,6 +32,8 @@ struct sv_loop {
     DevBuf gate;               // uint64: the last draw kernel whose grid is resident (its epoch = seq + 1)
     int64_t next = 0;          // sequence number of the next submitted batch
     int64_t pending = -1;      // the batch whose pipeline + road pass are not enqueued yet (see sv_loop_submit)
+    int jpeg_quality = 75;     // road = 7: the streams' quality and slot capacity (sv_loop_jpeg; 0 = the default slot)
+    int64_t jpeg_cap = 0;
 };
 
 // A stage of batch seq on its slot's stream: begin waits for the same stage of the batch before (on the other
@@ -78,12 +80,12 @@ int sv_loop_create(int device, const sv_loop_params* prm, const sv_camera* cam, 
     *out = nullptr;
     const sv_loop_params& q = *prm;
     if (q.frames < 1 || q.slots < 1 || q.slots > 8 || (q.source != 0 && q.source != 1) || q.prepass < 0 ||
-        q.prepass > 2 || q.road < 0 || q.road > 6 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
+        q.prepass > 2 || q.road < 0 || q.road > 7 || (q.step != 1 && q.step != 2) || q.trials < 0 || q.k < 1)
         return fail(SV_E_ARG, "sv_loop_create: bad parameters (frames >= 1, 1 <= slots <= 8, source 0/1, prepass "
-                              "0..2, road 0..6, step 1/2, trials >= 0, k >= 1)");
-    if (q.road == 6)   // the image tile's shape (sv_batch_tile would refuse it only after a batch's other stages)
+                              "0..2, road 0..7, step 1/2, trials >= 0, k >= 1)");
+    if (q.road >= 6)   // the image tile's shape (sv_batch_tile would refuse it only after a batch's other stages)
         if (const char* why = tile_check_shape(q.H, q.W))
-            return fail(SV_E_ARG, "sv_loop_create: road = 6 (the image tile) takes frames with %s", why);
+            return fail(SV_E_ARG, "sv_loop_create: road >= 6 (the image tile) takes frames with %s", why);
     // what a submit would only find out after enqueueing the input and pre-pass stages (the RANSAC and synthetic
     // input limits of batch_ransac_prepare / sv_batch_synth)
     if (q.trials > 4096 || q.k > 1024) return fail(SV_E_ARG, "sv_loop_create: RANSAC trials <= 4096, k <= 1024");
@@ -150,6 +152,16 @@ int sv_loop_road_mask(sv_loop* L, const uint8_t* mask) {
     return SV_OK;
 }
 
+int sv_loop_jpeg(sv_loop* L, int quality, int64_t cap_per_frame) {
+    if (!L) return fail(SV_E_ARG, "sv_loop_jpeg: null loop");
+    if (quality < 1 || quality > 100 || cap_per_frame < 0 || cap_per_frame > 0x7FFFFFFF)
+        return fail(SV_E_ARG, "sv_loop_jpeg: 1 <= quality <= 100, 0 <= cap_per_frame < 2^31");
+    if (L->next > 0) return fail(SV_E_STATE, "sv_loop_jpeg: set before the first sv_loop_submit");
+    L->jpeg_quality = quality;
+    L->jpeg_cap = cap_per_frame;
+    return SV_OK;
+}
+
 // The batch the next sv_loop_submit processes (source 0: the caller fills it first); waits on the host until
 // the batch that last used its slot has finished every stage.
 int sv_loop_acquire(sv_loop* L, sv_batch** out) {
@@ -190,8 +202,12 @@ static int loop_enqueue_tail(sv_loop* L, int64_t seq, uint64_t gate_epoch) {
     if (q.road >= 5) {   // the result image from the BGR and the obstacle stage (stereovision.py:181-209)
         if (int rc = sv_batch_result(b, 0)) return rc;
     }
-    if (q.road == 6) {   // batchImages' tile of the five pictures above (stereovision.py:216)
+    if (q.road >= 6) {   // batchImages' tile of the five pictures above (stereovision.py:216)
         if (int rc = sv_batch_tile(b, 0)) return rc;
+    }
+    if (q.road == 7) {   // the recording (loop.py:49-54,82-89): the tiles' JPEG streams, packed for one copy
+        if (int rc = sv_batch_jpeg(b, L->jpeg_quality, L->jpeg_cap, 0)) return rc;
+        if (int rc = sv_batch_jpeg_pack(b, 0)) return rc;
     }
     HIP_TRY(stage_end(L, seq, kLsRoad));
     if (L->pending == seq) L->pending = -1;

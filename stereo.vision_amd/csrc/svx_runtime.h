@@ -145,6 +145,7 @@ struct Device {
     DevBuf res;                       // sv_result_image: image, obstacle bitmap, vertices and info (ResultLayout)
     DevBuf tile;                      // sv_image_tile: the staged result image and the tile (TileLayout)
     DevBuf rsz;                       // sv_resize_linear_u8, sv_images_tile: tables, staged pictures, stack, output
+    DevBuf jpg;                       // sv_jpeg_encode: tables, the staged picture, the scratch and the stream
     DevBuf sg_l, sg_r, sg_out, sg_filt, sg_hist;   // host-frame SGBM / grey drop-ins
     SgbmBufs sg;
     Tables tables;
@@ -185,11 +186,13 @@ enum RoadLevel {
     kRoadCleaned,     // sv_batch_road_clean: cbits / cimg / cnz hold the clean-up of those images
     kRoadObstacles,   // sv_batch_road_hull: hbuf holds the obstacle stage of that clean-up
     kRoadResult,      // sv_batch_result: rimg holds the result image of that obstacle stage
-    kRoadTile         // sv_batch_tile: timg holds the image tile of that result image
+    kRoadTile,        // sv_batch_tile: timg holds the image tile of that result image
+    kRoadJpeg         // sv_batch_jpeg: jout / jsizes hold the JPEG streams of that tile
 };
 // the road chain's events in sv_batch::road_ev, made by a stage's first call: the clean-up's start, its kernel's
-// start / end and its end, then start / end of the obstacle stage, of the result image and of the image tile
-enum { kEvClean = 0, kEvHull = 4, kEvResult = 6, kEvTile = 8, kEvRoadCount = 10 };
+// start / end and its end, then start / end of the obstacle stage, of the result image, of the image tile and of its
+// JPEG streams
+enum { kEvClean = 0, kEvHull = 4, kEvResult = 6, kEvTile = 8, kEvJpeg = 10, kEvRoadCount = 12 };
 
 }  // namespace svx
 
@@ -222,7 +225,7 @@ struct sv_batch {
     bool rbits_fresh = false;   // rbits holds the bitmap of the current pipeline points
     DevBuf rbits, roff;         // the bitmap (frames x H x 32 words); the road pass's per-row walk offsets
     bool want_rmap = false, rmap_fresh = false;
-    RoadLevel road_level = kRoadNone;   // which of road / cimg / hbuf / rimg / timg belong to the current points
+    RoadLevel road_level = kRoadNone;   // which of road / cimg / hbuf / rimg / timg / jout belong to the current points
     hipEvent_t road_ev[kEvRoadCount] = {};
     // sanitiseRoadImage's clean-up (sv_batch_road_clean): the mask as a bitmap (behind its staged bytes), the packed
     // road images (when the pipeline wrote no bitmap), the cleaned bitmaps, images, walks (frames x ccap packed
@@ -240,6 +243,14 @@ struct sv_batch {
     DevBuf rimg;
     // the image tile (sv_batch_tile): frames x H / 2 rows of 3 Wu bytes, packed; made on first use
     DevBuf timg;
+    // the tile's JPEG streams (sv_batch_jpeg; rt_jpeg.hip): the tables and header of jquality (jhost: the host block
+    // they are copied from), the scratch of a chunk of jchunk frames, frames slots of jcap bytes, the sizes; the
+    // packed run and its frames + 1 offsets (sv_batch_jpeg_pack; jpacked: of the current streams)
+    DevBuf jconst, jwork, jout, jsizes, jpack, joffs;
+    std::vector<uint8_t> jhost;
+    int jquality = 0, jchunk = 0;
+    int64_t jcap = 0;
+    bool jpacked = false;
     // the cleaned disparity at a display size (sv_batch_resize_disp): frames x rd_h x rd_w bytes, packed, and the
     // coefficient tables of that size (svx_resize_host.h); made on first use. rdisp_fresh: it is the resize of what
     // `disp` holds now: whatever writes the batch's frames or cleans them again clears it.

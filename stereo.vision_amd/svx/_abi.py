@@ -98,6 +98,15 @@ SIGNATURES = {
     "sv_batch_tile": [P, I],
     "sv_batch_read_tile": [P, I, P],
     "sv_batch_tile_ms": [P, PF],
+    "sv_jpeg_bound": [I, I],
+    "sv_jpeg_encode": [P, I, I, I64, I, P, I64, PI64],
+    "sv_batch_jpeg": [P, I, I64, I],
+    "sv_batch_jpeg_sizes": [P, P],
+    "sv_batch_read_jpeg": [P, I, P, I64, PI64],
+    "sv_batch_jpeg_pack": [P, I],
+    "sv_batch_read_jpeg_packed": [P, P, I64, P, PI64],
+    "sv_batch_jpeg_ms": [P, PF],
+    "sv_loop_jpeg": [P, I, I64],
     "sv_resize_coefficients": [I, I, P, P, P, P],
     "sv_resize_linear_u8": [P, I, I, I, I, P, I, I],
     "sv_images_tile_shape": [I, I, I, ctypes.POINTER(I), ctypes.POINTER(I)],
@@ -178,7 +187,7 @@ SIGNATURES = {
     "sv_multi_pipeline": [I, P, P, ctypes.POINTER(Camera), ctypes.POINTER(Plane), I, D, I, I],
     "sv_comm_allreduce_i64": [P, P, I],
 }
-_RESTYPE = {"sv_version": ctypes.c_char_p, "sv_last_error": ctypes.c_char_p}
+_RESTYPE = {"sv_version": ctypes.c_char_p, "sv_last_error": ctypes.c_char_p, "sv_jpeg_bound": ctypes.c_int64}
 
 _lib = None
 

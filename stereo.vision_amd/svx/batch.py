@@ -347,6 +347,53 @@ class Batch:
         _abi.call("sv_batch_read_tile", self._h, frame, _abi.ptr(out))
         return out
 
+    def jpeg(self, quality=75, cap=None, sync=True):
+        """The baseline JPEG stream (loop.py:49-54,82-89: what the MJPG VideoWriter makes of a picture)
+        of every frame's tile, on the device, each into a slot of `cap` bytes (None: half the raw tile); after
+        tile(). A frame that overflows its slot is flagged in jpeg_sizes() and not written (sv_batch_jpeg)."""
+        _abi.call("sv_batch_jpeg", self._h, int(quality), 0 if cap is None else int(cap), int(sync))
+
+    def jpeg_ms(self):
+        """ms of the last jpeg(), from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_jpeg_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
+    def jpeg_sizes(self):
+        """The streams' lengths, (frames,) int32; negative: the frame overflowed its slot and needs minus that."""
+        out = np.empty(self.frames, np.int32)
+        _abi.call("sv_batch_jpeg_sizes", self._h, _abi.ptr(out))
+        return out
+
+    def read_jpeg(self, frame):
+        """One frame's stream as bytes (SvxError for a frame that overflowed its slot)."""
+        n = int(self.jpeg_sizes()[frame])
+        out = np.empty(max(abs(n), 1), np.uint8)
+        size = ctypes.c_int64(0)
+        _abi.call("sv_batch_read_jpeg", self._h, int(frame), _abi.ptr(out), out.size, ctypes.byref(size))
+        return out[: size.value].tobytes()
+
+    def read_jpegs_packed(self, out=None):
+        """(buffer, offsets, total): the batch's streams back to back in frame order, packed on the device and read in
+        one copy of exactly their bytes (sv_batch_jpeg_pack, sv_batch_read_jpeg_packed). offsets: (frames,) int64;
+        an overflowed frame contributes nothing. out: a uint8 array to read into (e.g. _abi.pinned_empty)."""
+        sizes = self.jpeg_sizes()
+        need = int(np.maximum(sizes, 0).sum(dtype=np.int64))
+        if out is None:
+            out = np.empty(max(need, 1), np.uint8)
+        offsets = np.empty(self.frames, np.int64)
+        total = ctypes.c_int64(0)
+        _abi.call("sv_batch_jpeg_pack", self._h, 1)
+        _abi.call("sv_batch_read_jpeg_packed", self._h, _abi.ptr(out), out.size, _abi.ptr(offsets), ctypes.byref(total))
+        return out, offsets, int(total.value)
+
+    def read_jpegs(self):
+        """Every frame's stream, a list of bytes in frame order (b"" for a frame that overflowed its slot), through
+        the pack: one device-to-host copy for the batch."""
+        buf, offsets, total = self.read_jpegs_packed()
+        ends = np.append(offsets[1:], total)
+        return [buf[int(a):int(z)].tobytes() for a, z in zip(offsets, ends)]
+
     def resize_disp(self, size, sync=True):
         """The cleaned disparity of every frame (read_disp) at size = (dh, dw), on the device: cv2.resize's 8-bit
         bilinear path in one launch over the resident frames (sv_batch_resize_disp). For a 390 x 889 cropped batch

@@ -383,6 +383,27 @@ def image_tile(disparity, imgL, road, cleaned, result):  # noqa: N803
     return out
 
 
+def jpeg_encode(img, quality=75):
+    """The baseline JPEG stream (bytes) of a picture, encoded on the GPU: what the MJPG VideoWriter of
+    loop.py:49-54,82-89 writes for one frame (include/svx.h, sv_jpeg_encode). img: (h, w, 3) uint8 BGR,
+    or (h, w) uint8 grey, encoded as B = G = R; 1..4096 each way. The scan's bytes are libjpeg's at this quality with
+    4:2:0 and one restart interval an MCU row; unpinned against cv2's own MJPG encoder."""
+    a = np.asarray(img)
+    if a.dtype != np.uint8:
+        raise TypeError(f"picture must be uint8, got {a.dtype}")
+    if a.ndim == 2:
+        a = np.repeat(a[:, :, None], 3, axis=2)
+    if a.ndim != 3 or a.shape[2] != 3:
+        raise ValueError(f"picture must be (h, w) or (h, w, 3), got {a.shape}")
+    a = np.ascontiguousarray(a)
+    h, w = a.shape[:2]
+    cap = int(_abi.lib().sv_jpeg_bound(h, w))
+    out = np.empty(max(cap, 1), np.uint8)
+    size = ctypes.c_int64(0)
+    _abi.call("sv_jpeg_encode", _abi.ptr(a), h, w, 3 * w, int(quality), _abi.ptr(out), cap, ctypes.byref(size))
+    return out[: size.value].tobytes()
+
+
 def _tile_images(imgList, size):  # noqa: N803
     """The five arrays of a batchImages list that the device takes (grey, BGR, grey, grey, BGR uint8, all of shape
     `size`, H and W multiples of 4, the second one already green wherever the third is set: what stereovision.py:216

@@ -13,7 +13,8 @@ in batches and every batch runs the non-cv2 stages of that function:
               Batch.read_road_clean; road="obstacles": + the obstacle stage, stereovision.py:170-189;
               Batch.read_road_hull; road="result": + the result image, stereovision.py:181-209;
               Batch.read_result; road="tile": + batchImages' tile of the five pictures, stereovision.py:216;
-              Batch.read_tile)
+              Batch.read_tile; road="video": + the tiles' JPEG streams, packed, for the MJPG recording of
+              loop.py:49-54,82-89; Batch.read_jpeg / read_jpegs, svx.video.VideoWriter.write_batch)
 
 FrameLoop keeps `slots` batches in flight, one HIP stream each; a stage of batch k waits for the same stage of
 batch k - 1 (a device event), and the RANSAC evaluation of batch k for batch k - 1's road pass, so with two slots
@@ -40,13 +41,13 @@ from .batch import CAMERA, Batch
 STAGES = ("input", "prepass", "maskpoints", "draw", "eval", "pipeline", "road")
 _SOURCES = {"caller": 0, "synth": 1}
 _PREPASS = {"none": 0, "previous": 1, "mean": 2}
-_ROAD = {"none": 0, "walk": 1, "map": 2, "clean": 3, "obstacles": 4, "result": 5, "tile": 6}
+_ROAD = {"none": 0, "walk": 1, "map": 2, "clean": 3, "obstacles": 4, "result": 5, "tile": 6, "video": 7}
 
 
 class FrameLoop:
     def __init__(self, frames, H=544, W=1024, step=1, slots=2, source="synth", prepass="previous", trials=600,
                  k=600, seed_base=0, point_thr=0.05, hist_thr=10, road="walk", carmask=None, camera=None,
-                 device=0, road_mask=None):
+                 device=0, road_mask=None, jpeg_quality=75, jpeg_cap=None):
         self.frames, self.H, self.W, self.step, self.slots, self.device = frames, H, W, step, slots, device
         prm = _abi.LoopParams(frames=frames, H=H, W=W, step=step, slots=slots, source=_SOURCES[source],
                               prepass=_PREPASS[prepass], trials=trials, k=k, seed_base=seed_base,
@@ -61,9 +62,12 @@ class FrameLoop:
                   ctypes.byref(h))
         self._h = h
         self._views = weakref.WeakSet()   # the Batch views handed out: invalidated by close()
-        if road_mask is not None:
+        if road_mask is not None or road == "video":
             try:
-                self.road_mask(road_mask)
+                if road == "video":   # the streams' quality and slot (None: half the raw tile), sv_loop_jpeg
+                    _abi.call("sv_loop_jpeg", self._h, int(jpeg_quality), 0 if jpeg_cap is None else int(jpeg_cap))
+                if road_mask is not None:
+                    self.road_mask(road_mask)
             except Exception:
                 self.close()
                 raise
