@@ -270,6 +270,39 @@ int64_t sv_jpeg_bound(int h, int w);
 int sv_jpeg_encode(const uint8_t* bgr, int h, int w, int64_t ld, int quality, uint8_t* out, int64_t cap,
                    int64_t* size);
 
+/* The decoder of the MJPG playback (svx.video.VideoCapture, the counterpart of the cv2.VideoWriter of
+ * loop.py:49-54,82-89; DESIGN §7.12, restated in tests/jpeg_decode_numpy.py): a baseline stream to the BGR picture
+ * libjpeg-turbo's default path decodes from it (slow-integer IDCT, "fancy" h2v2 chroma upsampling, table colour
+ * conversion), byte for byte for streams an encoder made from 8-bit pictures (checked against Pillow on the test
+ * list; samples far out of range are clamped, as libjpeg's SIMD code does). Accepted: SOF0, 8 bit, three components
+ * at 2 x 2, 1 x 1, 1 x 1 (4:2:0), one interleaved scan (Ss 0, Se 63, Ah = Al = 0), h and w 1 .. 4096, any 8-bit DQT
+ * (ids 0 .. 3), any baseline DHT (the Annex K tables when the stream has none, as MJPG frames of other writers),
+ * any DRI (without one the scan is a single interval: correct, and decoded by one lane), APPn and COM skipped.
+ * Everything else - progressive, arithmetic, 12 bit, one or four components, 4:2:2 / 4:4:4, several scans, 16-bit
+ * DQT, a segment that runs past the buffer - is refused by the host parser with SV_E_ARG and a message that names
+ * what was met, before anything is launched. Malformed entropy-coded data never faults: the frame's status is one
+ * of 1 a code in no table, 2 a DC size above 11 or an AC size above 10, 3 a run past coefficient 63, 4 a wrong
+ * number of RSTn, 5 RSTn out of sequence, 6 no EOI (the largest that applies; 0: decoded), and the pixels of a
+ * frame with a status are unspecified. */
+typedef struct sv_jpeg_desc {
+    int32_t h, w;
+    int32_t restart_interval; /* MCUs; 0: the stream has no DRI */
+    int32_t header_len;       /* SOI .. SOS: the entropy-coded bytes start here */
+} sv_jpeg_desc;
+/* On the host: what a stream of n bytes holds, or SV_E_ARG when it is not of the accepted kind. */
+int sv_jpeg_info(const uint8_t* stream, int64_t n, sv_jpeg_desc* desc);
+/* One host stream to one host picture of h x w (the stream's own size, else SV_E_ARG), rows ld >= 3 w bytes apart,
+ * decoded on the device; *status as above. SV_E_ARG for nulls, dimensions outside 1 .. 4096 or ld < 3 w. */
+int sv_jpeg_decode(const uint8_t* stream, int64_t n, uint8_t* bgr_out, int h, int w, int64_t ld, int32_t* status);
+/* `count` streams packed back to back (as sv_batch_read_jpeg_packed writes them; offsets: count + 1 ascending
+ * positions in packed, the last the end of the run) to count x h x w x 3 bytes of `out` and count statuses, on
+ * `device`: one upload of the streams, one read-back of the pictures. Every stream must be h x w, else SV_E_ARG. */
+int sv_jpeg_decode_many(int device, const uint8_t* packed, const int64_t* offsets, int count, int h, int w,
+                        uint8_t* out, int32_t* status);
+/* ms of the four kernels (marker scan, entropy walk, chroma planes, picture) of the device's last
+ * sv_jpeg_decode_many, from HIP events, added up over its chunks; SV_E_STATE before the first. */
+int sv_jpeg_decode_stage_ms(int device, float* ms4);
+
 /* cv2.resize's 8-bit INTER_LINEAR path at any scale, as tests/tile_numpy.py restates it (resize_linear_u8): a
  * float32 source coordinate, int16 coefficients of 11-bit fixed point rounded half to even, an int32 horizontal
  * pass, the vertical pass's two >> 16 products and a final + 2 >> 2. Parity with OpenCV itself is unpinned: cv2 is
@@ -633,6 +666,16 @@ int sv_batch_pair_shape(sv_batch* b, int H, int W);
  * own (y, x), cropped or not). */
 int sv_batch_upload_bgr_pair(sv_batch* b, int frame, const uint8_t* L, const uint8_t* R);
 int sv_batch_synth_bgr_pair(sv_batch* b, int64_t first_frame_id);
+/* The same storage filled from JPEG streams (sv_jpeg_decode_many's kind and layout: two packed runs of `count`
+ * streams of the pair shape, offsets of count + 1 entries each) decoded on the device into frames first ..
+ * first + count - 1: a tenth of sv_batch_upload_bgr_pair's bytes over the host link. status: count statuses of the
+ * left streams, then count of the right ones (sv_jpeg_decode). It invalidates what an upload invalidates (nothing:
+ * sv_batch_preprocess reads the pairs anew). sv_batch_decode_ms: the ms of the last call's kernels from HIP events.
+ * sv_batch_read_bgr_pair: one frame's stored pair back (2 x Hp x Wp x 3 bytes). */
+int sv_batch_decode_bgr_pair(sv_batch* b, int first, int count, const uint8_t* packedL, const int64_t* offsL,
+                             const uint8_t* packedR, const int64_t* offsR, int32_t* status);
+int sv_batch_decode_ms(sv_batch* b, float* ms);
+int sv_batch_read_bgr_pair(sv_batch* b, int frame, uint8_t* L, uint8_t* R);
 int sv_batch_preprocess(sv_batch* b, const uint8_t* lut, int sync);
 int sv_batch_synth_pair(sv_batch* b, int64_t first_frame_id);
 int sv_batch_upload_pair(sv_batch* b, int frame, const uint8_t* L, const uint8_t* R);

@@ -146,6 +146,9 @@ struct Device {
     DevBuf tile;                      // sv_image_tile: the staged result image and the tile (TileLayout)
     DevBuf rsz;                       // sv_resize_linear_u8, sv_images_tile: tables, staged pictures, stack, output
     DevBuf jpg;                       // sv_jpeg_encode: tables, the staged picture, the scratch and the stream
+    DevBuf jdin, jdwork, jdout;       // sv_jpeg_decode(_many): descriptors, tables and streams; scratch; pictures
+    float jd_ms[4] = {0, 0, 0, 0};    // the last sv_jpeg_decode_many's four kernels (sv_jpeg_decode_stage_ms)
+    bool jd_have_ms = false;
     DevBuf sg_l, sg_r, sg_out, sg_filt, sg_hist;   // host-frame SGBM / grey drop-ins
     SgbmBufs sg;
     Tables tables;
@@ -251,6 +254,11 @@ struct sv_batch {
     int jquality = 0, jchunk = 0;
     int64_t jcap = 0;
     bool jpacked = false;
+    // the decoder of sv_batch_decode_bgr_pair (rt_jpeg_dec.hip): descriptors, tables and streams of one side; the
+    // scratch of a chunk of frames; the ms of the last call's kernels
+    DevBuf jdin, jdwork;
+    float jd_ms = 0;
+    bool jd_have_ms = false;
     // the cleaned disparity at a display size (sv_batch_resize_disp): frames x rd_h x rd_w bytes, packed, and the
     // coefficient tables of that size (svx_resize_host.h); made on first use. rdisp_fresh: it is the resize of what
     // `disp` holds now: whatever writes the batch's frames or cleans them again clears it.

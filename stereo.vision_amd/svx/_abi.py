@@ -40,6 +40,12 @@ class HullInfo(ctypes.Structure):
                 ("tipx", ctypes.c_int64), ("tipy", ctypes.c_int64)]
 
 
+class JpegDesc(ctypes.Structure):
+    """sv_jpeg_desc (include/svx.h)."""
+    _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
+                ("header_len", ctypes.c_int32)]
+
+
 class Picture(ctypes.Structure):
     """sv_picture (include/svx.h)."""
     _fields_ = [("data", ctypes.c_void_p), ("h", ctypes.c_int), ("w", ctypes.c_int), ("channels", ctypes.c_int)]
@@ -107,6 +113,13 @@ SIGNATURES = {
     "sv_batch_read_jpeg_packed": [P, P, I64, P, PI64],
     "sv_batch_jpeg_ms": [P, PF],
     "sv_loop_jpeg": [P, I, I64],
+    "sv_jpeg_info": [P, I64, P],
+    "sv_jpeg_decode": [P, I64, P, I, I, I64, P],
+    "sv_jpeg_decode_many": [I, P, P, I, I, I, P, P],
+    "sv_jpeg_decode_stage_ms": [I, PF],
+    "sv_batch_decode_bgr_pair": [P, I, I, P, P, P, P, P],
+    "sv_batch_decode_ms": [P, PF],
+    "sv_batch_read_bgr_pair": [P, I, P, P],
     "sv_resize_coefficients": [I, I, P, P, P, P],
     "sv_resize_linear_u8": [P, I, I, I, I, P, I, I],
     "sv_images_tile_shape": [I, I, I, ctypes.POINTER(I), ctypes.POINTER(I)],

@@ -163,6 +163,34 @@ class Batch:
             raise ValueError(f"BGR pair must be {shape}")
         _abi.call("sv_batch_upload_bgr_pair", self._h, frame, _abi.ptr(L), _abi.ptr(R))
 
+    def decode_bgr_pair(self, first, left_streams, right_streams):
+        """BGR stereo pairs from baseline JPEG streams (lists of bytes, each of the pair shape), decoded on the
+        device into frames first .. first + n - 1 of the storage upload_bgr_pair fills (sv_batch_decode_bgr_pair;
+        DESIGN §7.12). Returns the (2, n) int32 statuses, left then right (0: decoded)."""
+        from .dropin import jpeg_pack
+        n = len(left_streams)
+        if n < 1 or len(right_streams) != n:
+            raise ValueError("as many right streams as left ones, at least one")
+        bl, ol = jpeg_pack(left_streams)
+        br, orr = jpeg_pack(right_streams)
+        status = np.zeros((2, n), np.int32)
+        _abi.call("sv_batch_decode_bgr_pair", self._h, int(first), n, _abi.ptr(bl), _abi.ptr(ol), _abi.ptr(br),
+                  _abi.ptr(orr), _abi.ptr(status))
+        return status
+
+    def decode_ms(self):
+        """ms of the last decode_bgr_pair()'s kernels, from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_decode_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
+    def read_bgr_pair(self, frame):
+        """One frame's stored BGR stereo pair (left, right), each the pair shape x 3."""
+        shape = getattr(self, "_pair", (self.H, self.W)) + (3,)
+        L, R = np.empty(shape, np.uint8), np.empty(shape, np.uint8)
+        _abi.call("sv_batch_read_bgr_pair", self._h, int(frame), _abi.ptr(L), _abi.ptr(R))
+        return L, R
+
     def synth_bgr_pair(self, first_frame_id=0):
         """Synthetic BGR stereo pairs for global frame ids first.. (device)."""
         _abi.call("sv_batch_synth_bgr_pair", self._h, int(first_frame_id))

@@ -404,6 +404,62 @@ def jpeg_encode(img, quality=75):
     return out[: size.value].tobytes()
 
 
+def jpeg_info(stream):
+    """(h, w, restart interval in MCUs, header length) of a baseline JPEG stream, parsed on the host
+    (include/svx.h, sv_jpeg_info); SvxError, naming what was met, for a stream outside the accepted kind."""
+    s = np.frombuffer(bytes(stream), np.uint8)
+    d = _abi.JpegDesc()
+    _abi.call("sv_jpeg_info", _abi.ptr(s) if s.size else None, s.size, ctypes.byref(d))
+    return int(d.h), int(d.w), int(d.restart_interval), int(d.header_len)
+
+
+def jpeg_pack(streams):
+    """A list of streams (bytes) as the packed run the decoder takes: (uint8 array, int64 offsets of len + 1)."""
+    offs = np.zeros(len(streams) + 1, np.int64)
+    np.cumsum([len(s) for s in streams], out=offs[1:])
+    buf = np.frombuffer(b"".join(bytes(s) for s in streams), np.uint8)
+    return (buf if buf.size else np.zeros(1, np.uint8)), offs
+
+
+def jpeg_decode(stream, with_status=False):
+    """The (h, w, 3) uint8 BGR picture of a baseline 4:2:0 JPEG stream (bytes), decoded on the GPU: libjpeg-turbo's
+    default pixels byte for byte (include/svx.h, sv_jpeg_decode), the counterpart of jpeg_encode and
+    what svx.video.VideoCapture.read() returns. A stream outside the accepted kind raises SvxError before anything
+    is launched; so does malformed entropy-coded data (a non-zero status), unless with_status is set: then the
+    result is (picture, status) and the picture of a frame with a status is unspecified."""
+    s = np.frombuffer(bytes(stream), np.uint8)
+    h, w, _, _ = jpeg_info(s)
+    out = np.empty((h, w, 3), np.uint8)
+    status = ctypes.c_int32(0)
+    _abi.call("sv_jpeg_decode", _abi.ptr(s), s.size, _abi.ptr(out), h, w, 3 * w, ctypes.byref(status))
+    if with_status:
+        return out, int(status.value)
+    if status.value:
+        raise _abi.SvxError(f"malformed JPEG scan (status {status.value})")
+    return out
+
+
+def jpeg_decode_many(streams, device=0):
+    """Streams of one size (a list of bytes) -> ((n, h, w, 3) uint8 BGR, (n,) int32 statuses): one upload, one
+    read-back (sv_jpeg_decode_many)."""
+    if not len(streams):
+        raise ValueError("no streams")
+    h, w, _, _ = jpeg_info(streams[0])
+    buf, offs = jpeg_pack(streams)
+    out = np.empty((len(streams), h, w, 3), np.uint8)
+    status = np.zeros(len(streams), np.int32)
+    _abi.call("sv_jpeg_decode_many", int(device), _abi.ptr(buf), _abi.ptr(offs), len(streams), h, w, _abi.ptr(out),
+              _abi.ptr(status))
+    return out, status
+
+
+def jpeg_decode_stage_ms(device=0):
+    """ms of the last jpeg_decode_many's four kernels: marker scan, entropy walk, chroma planes, picture."""
+    ms = (ctypes.c_float * 4)()
+    _abi.call("sv_jpeg_decode_stage_ms", int(device), ms)
+    return [float(v) for v in ms]
+
+
 def _tile_images(imgList, size):  # noqa: N803
     """The five arrays of a batchImages list that the device takes (grey, BGR, grey, grey, BGR uint8, all of shape
     `size`, H and W multiples of 4, the second one already green wherever the third is set: what stereovision.py:216
