@@ -178,6 +178,35 @@ int sv_road_obstacles(const uint8_t* cleaned, const uint8_t* disp, const sv_plan
  * out_xy[2] = the centre truncated toward zero. */
 int sv_min_circle_centre(const int32_t* pts, int64_t n, int32_t* out_xy);
 
+/* ---- the obstacle list: the components of the obstacle image, with box and range ---- */
+
+/* What the obstacle image holds, as a list (the reference stops at the picture; its brief asks for "detecting
+ * objects on the road"). Everything is an integer and exact.
+ *  - components: the 8-connected components of the non-zero pixels (cv2.connectedComponentsWithStats' default
+ *    connectivity; scipy.ndimage.label with a 3 x 3 structure of ones); pixels outside the image are background.
+ *  - per component: area = its pixels; x0, y0, x1, y1 = its inclusive box; first = y * W + x of its first pixel in
+ *    raster order; sx, sy = the sums of its pixels' x and of their y (the centroid is sx / area, sy / area, divided
+ *    by the caller).
+ *  - disparity, over the component's pixels with d > 0 (any u8 value counts): nd = their number, dmax = the
+ *    largest (the nearest point), dmed = the lower median, sorted(values)[(nd - 1) / 2]. All three are 0 when
+ *    nd == 0 or no disparity is given.
+ *  - the list: n = the number of components with area >= min_area, in full even when it exceeds cap; the list holds
+ *    the first min(n, cap) of them ordered by area descending, then by first ascending. Entries past the list's
+ *    length are not written. reserved is written as 0.
+ * No floating point on the device: metres are the caller's, Z = f B / dmed and X, Y those of the box's centre at
+ * that Z (functions.py:191-193; svx.dropin.obstacle_xyz). cv2's label numbering is not reproduced (cv2 is absent
+ * here; the list has the order above). The device labels runs of set bits of the packed bitmap by union-find
+ * (csrc/kernels/objects.hip). */
+typedef struct sv_obstacle {
+    int32_t x0, y0, x1, y1, area, first, nd, dmax, dmed, reserved;
+    int64_t sx, sy;
+} sv_obstacle;   /* 56 bytes */
+/* One host frame, synchronous. obstacles: H x W u8, non-zero = obstacle; disp (nullable): H x W u8; out: cap
+ * entries; *n as above. 2 <= W <= 4096, 1 <= H <= 4096, min_area >= 1, 1 <= cap <= 32; SV_E_ARG otherwise and for
+ * null obstacles, out or n, before anything is launched. */
+int sv_obstacle_list(const uint8_t* obstacles, const uint8_t* disp /* nullable */, int H, int W, int min_area,
+                     sv_obstacle* out, int cap, int32_t* n);
+
 /* ---- the result image (stereovision.py:181-209, functions.py:390-394, :424-431) ---- */
 
 /* The picture performStereoVision shows per frame: the left image dimmed with its obstacles tinted yellow
@@ -546,6 +575,21 @@ int sv_batch_read_road_hull(sv_batch* b, int frame, int32_t* hull_pts, int64_t c
                             uint8_t* obstacles, sv_hull_info* info);
 /* ms of the last sv_batch_road_hull from HIP events on the batch stream. Synchronises the batch stream. */
 int sv_batch_road_hull_ms(sv_batch* b, float* ms);
+/* The obstacle list (sv_obstacle_list) of every frame, on the device: one kernel that reads the obstacle stage's
+ * bitmaps and the batch's cleaned, unmasked disparity (what sv_batch_read_disp returns), and writes frames x cap
+ * entries and the counts into a buffer of its own. A side branch of the road chain: it needs a current obstacle
+ * stage (SV_E_STATE without sv_batch_road_hull after the last clean-up) and raises no level, so the result image
+ * and the tile neither need it nor undo it; a new sv_batch_road_hull, and whatever invalidates the obstacle stage,
+ * invalidates the list. min_area >= 1, 1 <= cap <= 32 (SV_E_ARG). The labelling scratch is sized by the frame's
+ * shape alone (csrc/svx_objects_host.h: at most 2 GiB, 1024 workgroups' worth), allocated by the first call. */
+int sv_batch_obstacle_list(sv_batch* b, int min_area, int cap, int sync);
+/* One frame's list: *n = its count in full, out (cap entries) = the first min(*n, cap) entries. A cap below the
+ * call's gives the head of the list; one above it is SV_E_ARG. SV_E_STATE without a current list. The first read
+ * after a call synchronises the batch stream and copies every frame's list to the host at once (56 cap + 4 bytes a
+ * frame); later reads of that call's lists touch no device. */
+int sv_batch_read_obstacle_list(sv_batch* b, int frame, sv_obstacle* out, int cap, int32_t* n);
+/* ms of the last sv_batch_obstacle_list from HIP events on the batch stream. Synchronises the batch stream. */
+int sv_batch_obstacle_list_ms(sv_batch* b, float* ms);
 /* The result image (sv_result_image) of every frame, on the device: one kernel that reads the batch's BGR (the
  * image the pipeline read its colours from; left unchanged) and the obstacle stage's bitmaps, vertices and infos,
  * and writes a buffer of its own (frames x H x W x 3 bytes, allocated by the first call). SV_E_STATE without a

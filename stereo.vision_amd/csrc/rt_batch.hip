@@ -266,7 +266,8 @@ int sv_batch_destroy(sv_batch* b) {
                       &b->pairL, &b->pairR, &b->rsidx, &b->rtri, &b->bgrL, &b->bgrR,
                       &b->glut, &b->ghist, &b->sgflags, &b->prev0buf, &b->rdbuf, &b->rbits, &b->roff, &b->raw, &b->rmask, &b->cpack,
                       &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff, &b->hbuf, &b->rimg, &b->timg, &b->rdisp, &b->rdtab,
-                      &b->jconst, &b->jwork, &b->jout, &b->jsizes, &b->jpack, &b->joffs, &b->jdin, &b->jdwork})
+                      &b->jconst, &b->jwork, &b->jout, &b->jsizes, &b->jpack, &b->joffs, &b->jdin, &b->jdwork, &b->owork,
+                      &b->olist})
         x->release();
     if (b->hcnt) (void)hipHostFree(b->hcnt);
     if (b->cnt_ev) (void)hipEventDestroy(b->cnt_ev);

@@ -142,6 +142,7 @@ struct Device {
     DevBuf disp, bgr, xyz, rgb, ctrl, xy, aux, aux2;
     DevBuf mbits;                     // sv_sanitise_road: the image, the cleaned image and the mask as bitmaps
     DevBuf hull;                      // sv_road_obstacles: bitmaps, vertices and info (HullLayout)
+    DevBuf objs, objwork;             // sv_obstacle_list: the bitmap, the entries and the count; the labelling scratch
     DevBuf res;                       // sv_result_image: image, obstacle bitmap, vertices and info (ResultLayout)
     DevBuf tile;                      // sv_image_tile: the staged result image and the tile (TileLayout)
     DevBuf rsz;                       // sv_resize_linear_u8, sv_images_tile: tables, staged pictures, stack, output
@@ -194,8 +195,8 @@ enum RoadLevel {
 };
 // the road chain's events in sv_batch::road_ev, made by a stage's first call: the clean-up's start, its kernel's
 // start / end and its end, then start / end of the obstacle stage, of the result image, of the image tile and of its
-// JPEG streams
-enum { kEvClean = 0, kEvHull = 4, kEvResult = 6, kEvTile = 8, kEvJpeg = 10, kEvRoadCount = 12 };
+// JPEG streams, of the obstacle list
+enum { kEvClean = 0, kEvHull = 4, kEvResult = 6, kEvTile = 8, kEvJpeg = 10, kEvObjects = 12, kEvRoadCount = 14 };
 
 }  // namespace svx
 
@@ -242,6 +243,14 @@ struct sv_batch {
     const FramePlane* hull_planes = nullptr;
     int hull_plane_stride = 0;
     HullPlane hull_shared{};
+    // the obstacle list (sv_batch_obstacle_list; rt_objects.hip), a side branch of the chain at kRoadObstacles: the
+    // labelling scratch (ObjLayout), frames x olist_cap entries with the frames' counts behind them; olist_fresh:
+    // they are of the current obstacle stage (sv_batch_road_hull clears it). olist_host: the whole of olist, copied
+    // by the first read after a call (4096 lists of 16 are 3.7 MB: one copy, not two small ones a frame)
+    DevBuf owork, olist;
+    std::vector<char> olist_host;
+    int olist_cap = 0;
+    bool olist_fresh = false, olist_host_fresh = false;
     // the result image (sv_batch_result): frames x H rows of 3 W bytes, the BGR's layout; made on first use
     DevBuf rimg;
     // the image tile (sv_batch_tile): frames x H / 2 rows of 3 Wu bytes, packed; made on first use

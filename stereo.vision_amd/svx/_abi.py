@@ -40,6 +40,17 @@ class HullInfo(ctypes.Structure):
                 ("tipx", ctypes.c_int64), ("tipy", ctypes.c_int64)]
 
 
+class Obstacle(ctypes.Structure):
+    """sv_obstacle (include/svx.h), 56 bytes; OBSTACLE_DTYPE is the same layout for numpy."""
+    _fields_ = [(k, ctypes.c_int32) for k in ("x0", "y0", "x1", "y1", "area", "first", "nd", "dmax", "dmed",
+                                              "reserved")] + [("sx", ctypes.c_int64), ("sy", ctypes.c_int64)]
+
+
+OBSTACLE_FIELDS = [(k, "<i4") for k in ("x0", "y0", "x1", "y1", "area", "first", "nd", "dmax", "dmed", "reserved")] \
+    + [("sx", "<i8"), ("sy", "<i8")]
+OBSTACLE_MAX_CAP = 32
+
+
 class JpegDesc(ctypes.Structure):
     """sv_jpeg_desc (include/svx.h)."""
     _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
@@ -83,6 +94,7 @@ SIGNATURES = {
     "sv_road_obstacles": [P, P, ctypes.POINTER(Plane), I, I, ctypes.POINTER(Camera), P, I64, P, P,
                           ctypes.POINTER(HullInfo)],
     "sv_min_circle_centre": [P, I64, P],
+    "sv_obstacle_list": [P, P, I, I, I, P, I, ctypes.POINTER(ctypes.c_int32)],
     "sv_result_image": [P, P, P, I64, ctypes.POINTER(HullInfo), I, I, P],
     "sv_batch_road_raster": [P, I],
     "sv_batch_nonzero": [P, I],
@@ -97,6 +109,9 @@ SIGNATURES = {
     "sv_batch_road_hull": [P, I],
     "sv_batch_read_road_hull": [P, I, P, I64, P, P, ctypes.POINTER(HullInfo)],
     "sv_batch_road_hull_ms": [P, PF],
+    "sv_batch_obstacle_list": [P, I, I, I],
+    "sv_batch_read_obstacle_list": [P, I, P, I, ctypes.POINTER(ctypes.c_int32)],
+    "sv_batch_obstacle_list_ms": [P, PF],
     "sv_batch_result": [P, I],
     "sv_batch_read_result": [P, I, P],
     "sv_batch_result_ms": [P, PF],
@@ -261,6 +276,18 @@ def hull_result(H, W, images, read):
     return {"hull": pts[: info.n].reshape(-1, 1, 2).copy(), "hull_mask": mask, "obstacles": obst,
             "centre": (int(info.cx), int(info.cy)) if info.valid & 1 else None,
             "tip": (int(info.tipx), int(info.tipy)) if info.valid & 2 else None, "valid": int(info.valid)}
+
+
+def obstacle_result(cap, read):
+    """(n, entries) as dropin.obstacle_list and Batch.read_obstacle_list return them, from read(out, cap, n), a call
+    of sv_obstacle_list / sv_batch_read_obstacle_list: n = the frame's components of at least min_area pixels,
+    entries = the first min(n, cap) of them as a structured array of OBSTACLE_FIELDS."""
+    import numpy as np
+    cap = int(cap)
+    out = np.zeros(max(cap, 1), np.dtype(OBSTACLE_FIELDS))
+    n = ctypes.c_int32(0)
+    read(out, cap, ctypes.byref(n))
+    return int(n.value), out[: min(int(n.value), cap)].copy()
 
 
 class _PinnedPool:

@@ -340,6 +340,27 @@ class Batch:
         return _abi.hull_result(self.H, self.W, images, lambda pts, cap, m, o, info: _abi.call(
             "sv_batch_read_road_hull", self._h, frame, _abi.ptr(pts), cap, _abi.ptr(m), _abi.ptr(o), info))
 
+    def obstacle_list(self, min_area=70, cap=16, sync=True):
+        """The obstacle list (dropin.obstacle_list) of every frame, on the device: the components of the obstacle
+        stage's bitmaps with box, area and, from the batch's cleaned disparity, range; after road_hull(). A new
+        road_hull(), and whatever invalidates it, invalidates the list."""
+        _abi.call("sv_batch_obstacle_list", self._h, int(min_area), int(cap), int(sync))
+        self._olist_cap = int(cap)
+
+    def obstacle_list_ms(self):
+        """ms of the last obstacle_list(), from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_obstacle_list_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
+    def read_obstacle_list(self, frame, cap=None):
+        """One frame's list: (n, entries), n the frame's count in full, entries the first min(n, cap) as a structured
+        array (dropin.obstacle_list). cap: at most obstacle_list()'s (the default); a smaller one gives the head."""
+        if cap is None:
+            cap = getattr(self, "_olist_cap", _abi.OBSTACLE_MAX_CAP)
+        return _abi.obstacle_result(cap, lambda out, c, n: _abi.call(
+            "sv_batch_read_obstacle_list", self._h, frame, _abi.ptr(out), c, n))
+
     def result(self, sync=True):
         """The result image (stereovision.py:181-209) of every frame, on the device: the batch's BGR dimmed, the
         obstacles tinted, the hull outlined and the glyph drawn; after road_hull(), on a batch with BGR."""

@@ -40,6 +40,8 @@ reference:
   circle; installed only with ``install(.., hull=True)``. ``road_obstacles`` gives the whole
   obstacle stage (hull, hull mask, obstacles, centre, glyph tip) of a cleaned road image,
   ``result_image`` the picture drawn from it (stereovision.py:181-209; array form only).
+  ``obstacle_list`` turns the obstacle image into a list of its components (box, area, range;
+  ``obstacle_xyz`` for metres): the reference has no such function, so nothing is installed.
 * ``batchImages(imgList, size)`` (functions.py:456-501): the five-picture tile of
   stereovision.py:216 on the GPU (``image_tile`` is its array form); other lists go to the
   function it replaced. Installed only with ``install(.., tiles=True)``.
@@ -322,6 +324,38 @@ def road_obstacles(cleaned, disparity=None, abc=None, camera=None):
     return _abi.hull_result(H, W, True, lambda pts, cap, m, o, info: _abi.call(
         "sv_road_obstacles", _abi.ptr(im), _abi.ptr(dp), pl, H, W, ctypes.byref(cam), _abi.ptr(pts), cap,
         _abi.ptr(m), _abi.ptr(o), info))
+
+
+def obstacle_list(obstacles, disparity=None, min_area=70, cap=16):
+    """The obstacle image (non-zero = obstacle; what road_obstacles returns) as a list, on the GPU: (n, entries).
+    n = the number of 8-connected components of at least min_area pixels (70 is ParticleCleansing's threshold);
+    entries = the first min(n, cap) of them, largest area first, then by first pixel, as a structured array with
+    x0, y0, x1, y1 (the inclusive box), area, first (y * W + x of the first pixel in raster order), nd, dmax, dmed
+    (number, maximum and lower median of the component's disparities > 0; 0 without any), sx, sy (the sums of the
+    pixels' x and y). 1 <= cap <= 32 (include/svx.h, sv_obstacle_list). obstacle_xyz gives an entry's metres."""
+    im = np.ascontiguousarray(_as_u8(obstacles, 2, "obstacles"))
+    H, W = im.shape
+    dp = None
+    if disparity is not None:
+        dp = np.ascontiguousarray(_as_u8(disparity, 2, "disparity"))
+        if dp.shape != im.shape:
+            raise ValueError(f"disparity shape {dp.shape} != image shape {im.shape}")
+    return _abi.obstacle_result(cap, lambda out, c, n: _abi.call(
+        "sv_obstacle_list", _abi.ptr(im), _abi.ptr(dp), H, W, int(min_area), _abi.ptr(out), c, n))
+
+
+def obstacle_xyz(entry, camera=None):
+    """(X, Y, Z) in metres of an obstacle_list entry, in float64 on the host: Z = f B / dmed, and X, Y those of the
+    box's centre at that Z (functions.py:191-193). None for dmed == 0 (no disparity under the component). camera:
+    (f, B, cw, ch); default: the installed module's, else the reference's constants."""
+    cam = _abi.Camera(*camera) if camera is not None else _camera()
+    dmed = int(entry["dmed"])
+    if dmed == 0:
+        return None
+    z = (cam.f * cam.B) / dmed
+    cx = (int(entry["x0"]) + int(entry["x1"])) / 2.0
+    cy = (int(entry["y0"]) + int(entry["y1"])) / 2.0
+    return ((cx - cam.cw) * z) / cam.f, ((cy - cam.ch) * z) / cam.f, z
 
 
 def result_image(imgL, obstacles, hull, centre=None, tip=None):  # noqa: N803
