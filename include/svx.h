@@ -207,6 +207,40 @@ typedef struct sv_obstacle {
 int sv_obstacle_list(const uint8_t* obstacles, const uint8_t* disp /* nullable */, int H, int W, int min_area,
                      sv_obstacle* out, int cap, int32_t* n);
 
+/* ---- the ground grid: top-down occupancy of obstacles and road ---- */
+
+/* The obstacle image and the cleaned road image laid out on the ground plane (the reference stops at the picture;
+ * a planner, a logger or a display asks, for each lateral position, what is occupied and how near). A grid is nz
+ * rows of nx square cells of `cell` metres: cell (iz, ix) covers X in [x0 + ix cell, x0 + (ix + 1) cell) and Z in
+ * [z0 + iz cell, z0 + (iz + 1) cell); row 0 is the nearest. cell finite and > 0, x0 and z0 finite, nx, nz >= 1,
+ * nx * nz <= 8192 (two uint32 planes of the cells live in 64 KB of LDS). The default (a null grid) is 16 m across
+ * and 32 m ahead in cells of 0.25 m: x0 = -8, z0 = 0, cell = 0.25, nx = 64, nz = 128.
+ *  - a pixel (y, x) with d = disp[y, x] > 0 lies, in float64 and in the order of functions.py:191-192, at
+ *    Z = (f * B) / d, X = ((x - cw) * Z) / f; iz = floor((Z - z0) / cell), ix = floor((X - x0) / cell); it is in the
+ *    grid iff 0 <= ix < nx and 0 <= iz < nz, compared as doubles (floor, not truncation: a negative quotient is
+ *    outside, not cell 0). x and y are indices of the frame as given (a cropped frame: the crop's own).
+ *  - obst[iz * nx + ix]: the obstacle image's non-zero pixels with d > 0 in the cell; road[..]: the same count for
+ *    the road image. Full 32-bit counts.
+ *  - nearest[ix]: the smallest iz with obst[iz * nx + ix] >= min_count (min_count >= 1), else -1.
+ *  - info[4]: obstacle pixels in the grid; obstacle pixels with d > 0 outside it; obstacle pixels with d == 0; road
+ *    pixels in the grid. So sum(obst) == info[0], info[0] + info[1] + info[2] == the obstacle image's non-zero
+ *    pixels, sum(road) == info[3].
+ * The device does no floating point: the host builds the mapping (d, x) -> ix and d -> iz once per (camera, grid,
+ * W) in float64 (csrc/svx_ground_host.h), cached per device, and the kernel (csrc/kernels/ground.hip) looks it up.
+ * Metres are the caller's (svx.dropin.ground_grid_axes gives the cells' centres). */
+typedef struct sv_grid {
+    double x0, z0, cell;
+    int32_t nx, nz;
+} sv_grid;   /* 32 bytes */
+/* One host frame, synchronous. obstacles: H x W u8, non-zero = obstacle; road (nullable): H x W u8, non-zero = road;
+ * disp: H x W u8; grid (nullable: the default). Outputs: obst, road_out (nullable): nz x nx uint32; nearest: nx int32;
+ * info: 4 int32. 2 <= W <= 4096, 1 <= H <= 4096; SV_E_ARG otherwise, for a null obstacles, disp, cam, obst, nearest or
+ * info, a grid out of range, min_count < 1 or a camera whose f or B is not finite and positive, before anything is
+ * launched. */
+int sv_ground_grid(const uint8_t* obstacles, const uint8_t* road /* nullable */, const uint8_t* disp, int H, int W,
+                   const sv_camera* cam, const sv_grid* grid /* nullable */, int min_count, uint32_t* obst,
+                   uint32_t* road_out /* nullable */, int32_t* nearest, int32_t* info);
+
 /* ---- the result image (stereovision.py:181-209, functions.py:390-394, :424-431) ---- */
 
 /* The picture performStereoVision shows per frame: the left image dimmed with its obstacles tinted yellow
@@ -590,6 +624,24 @@ int sv_batch_obstacle_list(sv_batch* b, int min_area, int cap, int sync);
 int sv_batch_read_obstacle_list(sv_batch* b, int frame, sv_obstacle* out, int cap, int32_t* n);
 /* ms of the last sv_batch_obstacle_list from HIP events on the batch stream. Synchronises the batch stream. */
 int sv_batch_obstacle_list_ms(sv_batch* b, float* ms);
+/* The ground grid (sv_ground_grid) of every frame, on the device: one kernel that reads the obstacle stage's
+ * obstacle bitmap, the clean-up's cleaned bitmap and the batch's cleaned, unmasked disparity (what
+ * sv_batch_read_disp returns; x and y are the batch's own indices), and writes a buffer of its own, frames x
+ * (2 nx nz + nx + 4) x 4 bytes, allocated by the first call: every frame's two planes, then every frame's nearest
+ * profile, then every frame's info. grid: nullable (the default). A side branch of the road chain with the obstacle
+ * list's state rules: it needs a current obstacle stage (SV_E_STATE without sv_batch_road_hull after the last
+ * clean-up) and raises no level, so the result image, the tile, the JPEG streams and the list neither need it nor
+ * undo it; a new sv_batch_road_hull, and whatever invalidates the obstacle stage, invalidates the grid. SV_E_ARG as
+ * for sv_ground_grid. */
+int sv_batch_ground_grid(sv_batch* b, const sv_camera* cam, const sv_grid* grid, int min_count, int sync);
+/* One frame's grid; every pointer is nullable. obst, road: nz x nx uint32; nearest: nx int32; info: 4 int32, of the
+ * last sv_batch_ground_grid's grid. SV_E_STATE without a current grid. Synchronises the batch stream. */
+int sv_batch_read_ground_grid(sv_batch* b, int frame, uint32_t* obst, uint32_t* road, int32_t* nearest,
+                              int32_t* info);
+/* Every frame's nearest profile in one copy: out = frames x nx int32. */
+int sv_batch_read_ground_nearest(sv_batch* b, int32_t* out);
+/* ms of the last sv_batch_ground_grid from HIP events on the batch stream. Synchronises the batch stream. */
+int sv_batch_ground_grid_ms(sv_batch* b, float* ms);
 /* The result image (sv_result_image) of every frame, on the device: one kernel that reads the batch's BGR (the
  * image the pipeline read its colours from; left unchanged) and the obstacle stage's bitmaps, vertices and infos,
  * and writes a buffer of its own (frames x H x W x 3 bytes, allocated by the first call). SV_E_STATE without a

@@ -267,7 +267,7 @@ int sv_batch_destroy(sv_batch* b) {
                       &b->glut, &b->ghist, &b->sgflags, &b->prev0buf, &b->rdbuf, &b->rbits, &b->roff, &b->raw, &b->rmask, &b->cpack,
                       &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff, &b->hbuf, &b->rimg, &b->timg, &b->rdisp, &b->rdtab,
                       &b->jconst, &b->jwork, &b->jout, &b->jsizes, &b->jpack, &b->joffs, &b->jdin, &b->jdwork, &b->owork,
-                      &b->olist})
+                      &b->olist, &b->gbuf})
         x->release();
     if (b->hcnt) (void)hipHostFree(b->hcnt);
     if (b->cnt_ev) (void)hipEventDestroy(b->cnt_ev);

@@ -424,6 +424,7 @@ int sv_batch_road_hull(sv_batch* b, int sync) {
     HIP_TRY(stage_events(b, kEvHull, 2, &hev));
     b->road_level = kRoadCleaned;
     b->olist_fresh = false;   // the obstacle list (rt_objects.hip) is of the bitmaps about to be overwritten
+    b->ggrid_fresh = false;   // ... and so is the ground grid (rt_ground.hip)
     const HullLayout l = hull_layout(b->H, b->Wu, b->frames, false);
     HIP_TRY(b->hbuf.ensure(l.bytes));
     char* base = b->hbuf.as<char>();

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/svx.h"
+#include "svx_ground_host.h"
 #include "svx_hull.h"
 #include "svx_launch.h"
 #include "svx_sgbm.h"
@@ -134,6 +135,16 @@ struct Tables {
     DevBuf dxT, dyT;   // transposed (launch_delta_transpose): the resident pipeline's lane-contiguous delta stage
 };
 
+// The ground grid's mapping (svx_ground_host.h: the folded cell table) of one (camera, grid, W), made on the host in
+// fp64.
+struct GroundMap {
+    bool valid = false;
+    int W = 0;
+    sv_camera cam{};
+    sv_grid grid{};
+    DevBuf tab;
+};
+
 struct Device {
     bool init = false;
     hipStream_t stream = nullptr;
@@ -143,6 +154,8 @@ struct Device {
     DevBuf mbits;                     // sv_sanitise_road: the image, the cleaned image and the mask as bitmaps
     DevBuf hull;                      // sv_road_obstacles: bitmaps, vertices and info (HullLayout)
     DevBuf objs, objwork;             // sv_obstacle_list: the bitmap, the entries and the count; the labelling scratch
+    DevBuf ground;                    // sv_ground_grid: the two bitmaps, the planes, the profile and the totals
+    GroundMap gmap;                   // the ground grid's mapping, shared with the device's batches (ensure_ground_map)
     DevBuf res;                       // sv_result_image: image, obstacle bitmap, vertices and info (ResultLayout)
     DevBuf tile;                      // sv_image_tile: the staged result image and the tile (TileLayout)
     DevBuf rsz;                       // sv_resize_linear_u8, sv_images_tile: tables, staged pictures, stack, output
@@ -167,6 +180,9 @@ int dev_get(int device, Device** out);
 int current_device(int* dev);
 // Delta tables for (H, W, camera), built on the device in fp64 (tables.hip).
 int ensure_tables(Device& d, int H, int W, const sv_camera& cam, hipStream_t s);
+// The ground grid's mapping for (camera, grid, W) in d.gmap (rt_ground.hip), under the device's mutex. A new key
+// waits for the whole device first: a batch's launch may still be reading the mapping it replaces.
+int ensure_ground_map(Device& d, const sv_camera& cam, const sv_grid& grid, int W);
 
 // A device's scratch + stream, under its mutex: every drop-in's prologue.
 struct Locked {
@@ -195,8 +211,11 @@ enum RoadLevel {
 };
 // the road chain's events in sv_batch::road_ev, made by a stage's first call: the clean-up's start, its kernel's
 // start / end and its end, then start / end of the obstacle stage, of the result image, of the image tile and of its
-// JPEG streams, of the obstacle list
-enum { kEvClean = 0, kEvHull = 4, kEvResult = 6, kEvTile = 8, kEvJpeg = 10, kEvObjects = 12, kEvRoadCount = 14 };
+// JPEG streams, of the obstacle list, of the ground grid
+enum {
+    kEvClean = 0, kEvHull = 4, kEvResult = 6, kEvTile = 8, kEvJpeg = 10, kEvObjects = 12, kEvGround = 14,
+    kEvRoadCount = 16
+};
 
 }  // namespace svx
 
@@ -251,6 +270,11 @@ struct sv_batch {
     std::vector<char> olist_host;
     int olist_cap = 0;
     bool olist_fresh = false, olist_host_fresh = false;
+    // the ground grid (sv_batch_ground_grid; rt_ground.hip), a side branch like the list: the results of ggrid
+    // (GroundLayout); ggrid_fresh: they are of the current obstacle stage (sv_batch_road_hull clears it)
+    DevBuf gbuf;
+    sv_grid ggrid{};
+    bool ggrid_fresh = false;
     // the result image (sv_batch_result): frames x H rows of 3 W bytes, the BGR's layout; made on first use
     DevBuf rimg;
     // the image tile (sv_batch_tile): frames x H / 2 rows of 3 Wu bytes, packed; made on first use

@@ -51,6 +51,23 @@ OBSTACLE_FIELDS = [(k, "<i4") for k in ("x0", "y0", "x1", "y1", "area", "first",
 OBSTACLE_MAX_CAP = 32
 
 
+class Grid(ctypes.Structure):
+    """sv_grid (include/svx.h), 32 bytes: nz rows of nx square cells of `cell` metres from (x0, z0)."""
+    _fields_ = [("x0", ctypes.c_double), ("z0", ctypes.c_double), ("cell", ctypes.c_double),
+                ("nx", ctypes.c_int32), ("nz", ctypes.c_int32)]
+
+
+DEFAULT_GRID = (-8.0, 0.0, 0.25, 64, 128)   # 16 m across, 32 m ahead (include/svx.h, sv_ground_grid)
+
+
+def as_grid(grid):
+    """A Grid from None (the default), a Grid or (x0, z0, cell, nx, nz)."""
+    if isinstance(grid, Grid):
+        return grid
+    x0, z0, cell, nx, nz = DEFAULT_GRID if grid is None else grid
+    return Grid(float(x0), float(z0), float(cell), int(nx), int(nz))
+
+
 class JpegDesc(ctypes.Structure):
     """sv_jpeg_desc (include/svx.h)."""
     _fields_ = [("h", ctypes.c_int32), ("w", ctypes.c_int32), ("restart_interval", ctypes.c_int32),
@@ -95,6 +112,7 @@ SIGNATURES = {
                           ctypes.POINTER(HullInfo)],
     "sv_min_circle_centre": [P, I64, P],
     "sv_obstacle_list": [P, P, I, I, I, P, I, ctypes.POINTER(ctypes.c_int32)],
+    "sv_ground_grid": [P, P, P, I, I, ctypes.POINTER(Camera), ctypes.POINTER(Grid), I, P, P, P, P],
     "sv_result_image": [P, P, P, I64, ctypes.POINTER(HullInfo), I, I, P],
     "sv_batch_road_raster": [P, I],
     "sv_batch_nonzero": [P, I],
@@ -112,6 +130,10 @@ SIGNATURES = {
     "sv_batch_obstacle_list": [P, I, I, I],
     "sv_batch_read_obstacle_list": [P, I, P, I, ctypes.POINTER(ctypes.c_int32)],
     "sv_batch_obstacle_list_ms": [P, PF],
+    "sv_batch_ground_grid": [P, ctypes.POINTER(Camera), ctypes.POINTER(Grid), I, I],
+    "sv_batch_read_ground_grid": [P, I, P, P, P, P],
+    "sv_batch_read_ground_nearest": [P, P],
+    "sv_batch_ground_grid_ms": [P, PF],
     "sv_batch_result": [P, I],
     "sv_batch_read_result": [P, I, P],
     "sv_batch_result_ms": [P, PF],
@@ -288,6 +310,19 @@ def obstacle_result(cap, read):
     n = ctypes.c_int32(0)
     read(out, cap, ctypes.byref(n))
     return int(n.value), out[: min(int(n.value), cap)].copy()
+
+
+def ground_result(grid, read):
+    """{"obst", "road": (nz, nx) uint32, "nearest": (nx,) int32, "info": (4,) int32} as dropin.ground_grid and
+    Batch.read_ground_grid return them, from read(obst, road, nearest, info), a call of sv_ground_grid /
+    sv_batch_read_ground_grid."""
+    import numpy as np
+    # (a grid out of range is the library's to refuse, before it writes anything: its arrays are placeholders)
+    nz, nx = (grid.nz, grid.nx) if grid.nx >= 1 and grid.nz >= 1 and grid.nx * grid.nz <= 8192 else (1, 1)
+    out = {"obst": np.zeros((nz, nx), np.uint32), "road": np.zeros((nz, nx), np.uint32),
+           "nearest": np.zeros(nx, np.int32), "info": np.zeros(4, np.int32)}
+    read(out["obst"], out["road"], out["nearest"], out["info"])
+    return out
 
 
 class _PinnedPool:

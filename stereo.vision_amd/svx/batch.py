@@ -361,6 +361,36 @@ class Batch:
         return _abi.obstacle_result(cap, lambda out, c, n: _abi.call(
             "sv_batch_read_obstacle_list", self._h, frame, _abi.ptr(out), c, n))
 
+    def ground_grid(self, grid=None, min_count=1, camera=None, sync=True):
+        """The ground grid (dropin.ground_grid) of every frame, on the device: the obstacle stage's obstacles and the
+        clean-up's road laid out on the ground plane through the batch's cleaned disparity; after road_hull(). grid:
+        (x0, z0, cell, nx, nz), default (-8, 0, 0.25, 64, 128). A new road_hull(), and whatever invalidates it,
+        invalidates the grid; result(), tile() and obstacle_list() leave it alone."""
+        cam = camera or CAMERA
+        g = _abi.as_grid(grid)
+        _abi.call("sv_batch_ground_grid", self._h, ctypes.byref(cam), ctypes.byref(g), int(min_count), int(sync))
+        self._ggrid = g
+
+    def ground_grid_ms(self):
+        """ms of the last ground_grid(), from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_ground_grid_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
+    def read_ground_grid(self, frame):
+        """One frame's grid: {"obst", "road": (nz, nx) uint32, "nearest": (nx,) int32, "info": (4,) int32}
+        (dropin.ground_grid), of the last ground_grid()'s grid."""
+        g = getattr(self, "_ggrid", None) or _abi.as_grid(None)
+        return _abi.ground_result(g, lambda o, r, n, i: _abi.call(
+            "sv_batch_read_ground_grid", self._h, frame, _abi.ptr(o), _abi.ptr(r), _abi.ptr(n), _abi.ptr(i)))
+
+    def read_ground_nearest(self):
+        """Every frame's nearest profile in one copy: (frames, nx) int32."""
+        g = getattr(self, "_ggrid", None) or _abi.as_grid(None)
+        out = np.zeros((self.frames, g.nx), np.int32)
+        _abi.call("sv_batch_read_ground_nearest", self._h, _abi.ptr(out))
+        return out
+
     def result(self, sync=True):
         """The result image (stereovision.py:181-209) of every frame, on the device: the batch's BGR dimmed, the
         obstacles tinted, the hull outlined and the glyph drawn; after road_hull(), on a batch with BGR."""

@@ -42,6 +42,8 @@ reference:
   ``result_image`` the picture drawn from it (stereovision.py:181-209; array form only).
   ``obstacle_list`` turns the obstacle image into a list of its components (box, area, range;
   ``obstacle_xyz`` for metres): the reference has no such function, so nothing is installed.
+  ``ground_grid`` lays the obstacle and road images out on the ground plane (counts a cell, the
+  nearest occupied range a column; ``ground_grid_axes`` for metres): nothing is installed either.
 * ``batchImages(imgList, size)`` (functions.py:456-501): the five-picture tile of
   stereovision.py:216 on the GPU (``image_tile`` is its array form); other lists go to the
   function it replaced. Installed only with ``install(.., tiles=True)``.
@@ -356,6 +358,39 @@ def obstacle_xyz(entry, camera=None):
     cx = (int(entry["x0"]) + int(entry["x1"])) / 2.0
     cy = (int(entry["y0"]) + int(entry["y1"])) / 2.0
     return ((cx - cam.cw) * z) / cam.f, ((cy - cam.ch) * z) / cam.f, z
+
+
+def ground_grid(obstacles, disp, road=None, camera=None, grid=None, min_count=1):
+    """The obstacle image (non-zero = obstacle) and, if given, the road image laid out on the ground plane, on the
+    GPU: {"obst", "road": (nz, nx) uint32, the pixels with d > 0 that fall in each cell (row 0 nearest; road all zero
+    without a road image), "nearest": (nx,) int32, the smallest iz with obst[iz, ix] >= min_count or -1, "info":
+    (4,) int32, obstacle pixels in the grid, with d > 0 outside it, with d == 0, road pixels in the grid}. A pixel
+    (y, x) with d = disp[y, x] > 0 is at Z = f B / d, X = (x - cw) Z / f (functions.py:191-192, float64) and in cell
+    iz = floor((Z - z0) / cell), ix = floor((X - x0) / cell). camera: (f, B, cw, ch), default: the installed
+    module's, else the reference's constants; grid: (x0, z0, cell, nx, nz), nx nz <= 8192, default (-8, 0, 0.25,
+    64, 128) (include/svx.h, sv_ground_grid). ground_grid_axes gives the cells' centres in metres."""
+    im = np.ascontiguousarray(_as_u8(obstacles, 2, "obstacles"))
+    H, W = im.shape
+    dp = np.ascontiguousarray(_as_u8(disp, 2, "disparity"))
+    if dp.shape != im.shape:
+        raise ValueError(f"disparity shape {dp.shape} != image shape {im.shape}")
+    rd = None
+    if road is not None:
+        rd = np.ascontiguousarray(_as_u8(road, 2, "road"))
+        if rd.shape != im.shape:
+            raise ValueError(f"road shape {rd.shape} != image shape {im.shape}")
+    cam = _abi.Camera(*camera) if camera is not None else _camera()
+    g = _abi.as_grid(grid)
+    return _abi.ground_result(g, lambda o, r, n, i: _abi.call(
+        "sv_ground_grid", _abi.ptr(im), _abi.ptr(rd), _abi.ptr(dp), H, W, ctypes.byref(cam), ctypes.byref(g),
+        int(min_count), _abi.ptr(o), _abi.ptr(r), _abi.ptr(n), _abi.ptr(i)))
+
+
+def ground_grid_axes(grid=None):
+    """(X, Z): the cell centres of a ground grid in metres, X of nx and Z of nz float64 values (host only)."""
+    g = _abi.as_grid(grid)
+    return (g.x0 + (np.arange(g.nx, dtype=np.float64) + 0.5) * g.cell,
+            g.z0 + (np.arange(g.nz, dtype=np.float64) + 0.5) * g.cell)
 
 
 def result_image(imgL, obstacles, hull, centre=None, tip=None):  # noqa: N803
