@@ -406,6 +406,33 @@ typedef struct {
 int sv_images_tile_shape(int count, int H, int W, int* oh, int* ow);
 int sv_images_tile(const sv_picture* pics, int count, int H, int W, uint8_t* out);
 
+/* ---- stereo rectification: the map pair and the remap (no reference function: its dataset ships rectified) ---- */
+/* The maps are OpenCV's fixed-point pair, so cv2.initUndistortRectifyMap(..., m1type=CV_16SC2)'s can be handed in as
+ * they are: xy is dh x dw x 2 int16 holding (sx, sy), frac is dh x dw uint16 holding fy * 32 + fx, 0 <= fx, fy < 32;
+ * a frac entry >= 1024 is SV_E_ARG wherever a map is taken. The remap is cv2.remap's 8-bit INTER_LINEAR path with
+ * BORDER_CONSTANT 0 as tests/rectify_numpy.py restates it: per destination pixel and channel, in int32,
+ *   S(i, j) = src[sy + j][sx + i] inside the source, else 0                                  (i, j in {0, 1})
+ *   dst = (w00 S(0,0) + w10 S(1,0) + w01 S(0,1) + w11 S(1,1) + 16384) >> 15
+ *   w00 = 32 (32 - fx)(32 - fy), w10 = 32 fx (32 - fy), w01 = 32 (32 - fx) fy, w11 = 32 fx fy   (their sum is 32768)
+ * Parity with OpenCV itself is unpinned: cv2 is absent here; every result is bit for bit the restatement's.
+ * sv_rectify_map: initUndistortRectifyMap on the host in float64 (no device): K9 the raw camera's 3 x 3 matrix (fx,
+ * fy, u0, v0 are read), D8 its distortion k1, k2, p1, p2, k3, k4, k5, k6 (the rational model with tangential terms),
+ * R9 the rectifying rotation, P9 the new 3 x 3 camera matrix. Per destination (u, v): [X Y W] = inv(P R) [u v 1],
+ * x = X / W, y = Y / W, r2 = x x + y y, kr = (1 + ((k3 r2 + k2) r2 + k1) r2) / (1 + ((k6 r2 + k5) r2 + k4) r2),
+ * xd = x kr + p1 (2 x y) + p2 (r2 + 2 x x), yd = y kr + p1 (r2 + 2 y y) + p2 (2 x y), mu = fx xd + u0,
+ * mv = fy yd + v0; iu = rint(32 mu), iv = rint(32 mv) half to even, clamped to [-32768 * 32, 32767 * 32 + 31], a
+ * non-finite value becoming the lower bound; sx = iu >> 5, fx = iu & 31, likewise y. The inverse is the adjugate over
+ * the determinant (parity with OpenCV's LU inverse to the last ulp is unpinned). SV_E_ARG for a NULL pointer, dh or dw
+ * outside 1 .. 8192, or a zero or non-finite determinant of P R; nothing is written then. */
+int sv_rectify_map(const double* K9, const double* D8, const double* R9, const double* P9, int dh, int dw, int16_t* xy,
+                   uint16_t* frac);
+/* n packed pictures of sh x sw x channels remapped through one map into n packed pictures of dh x dw x channels, one
+ * launch, synchronous. channels is 1 or 3; source and destination dimensions 1 .. 8192; the destination has the map's
+ * shape, which need not be the source's. SV_E_ARG for a NULL pointer, dst overlapping src, n < 1, channels other than
+ * 1 or 3, a dimension out of range or a frac entry >= 1024, with nothing launched. */
+int sv_remap_u8(const uint8_t* src, int n, int sh, int sw, int channels, const int16_t* xy, const uint16_t* frac,
+                int dh, int dw, uint8_t* dst);
+
 /* ---- the stages a2-a6 one by one (the stage drop-ins) ---------------------- */
 
 /* calculatePointErrors (functions.py:300-312): out[i] = |(P_i . abc - 1) / d|
@@ -772,6 +799,27 @@ int sv_batch_decode_bgr_pair(sv_batch* b, int first, int count, const uint8_t* p
                              const uint8_t* packedR, const int64_t* offsR, int32_t* status);
 int sv_batch_decode_ms(sv_batch* b, float* ms);
 int sv_batch_read_bgr_pair(sv_batch* b, int frame, uint8_t* L, uint8_t* R);
+/* Rectification of the stored BGR pairs, between upload / decode / synth and sv_batch_preprocess, for cameras that
+ * deliver distorted, unaligned pictures (the maps and the remap: sv_rectify_map, sv_remap_u8 above).
+ * sv_batch_rectify_maps: the two eyes' maps of the pair shape (Hp x Wp x 2 int16 and Hp x Wp uint16 each), uploaded
+ * and kept until replaced; sv_batch_pair_shape with a new shape drops them. SV_E_ARG for a NULL pointer or a frac
+ * entry >= 1024.
+ * sv_batch_rectify: every frame's pair through its eye's map, both eyes in one launch. The gather cannot run in
+ * place: the first call allocates a second store of the pairs' size (2 x frames x Hp x Wp x 3 bytes) and the two
+ * change places, so afterwards sv_batch_read_bgr_pair returns the rectified pairs and sv_batch_preprocess consumes
+ * them, while the pictures as they came are kept: a pair written later lands beside them, and the next call
+ * rectifies every frame from its raw picture. SV_E_STATE without maps of the current pair shape, without a BGR pair
+ * store, or when no pair was uploaded, decoded or generated since the last call (the pairs are rectified already).
+ * The stores change back when a write of a pair BEGINS (once its arguments are accepted), not when it succeeds: after
+ * an upload whose copy fails, or a decode whose streams give statuses or that fails midway, sv_batch_read_bgr_pair
+ * and sv_batch_preprocess see the raw pictures of every frame until the next sv_batch_rectify, which is allowed.
+ * The camera to hand to the later stages is the rectified pair's: f = P[0][0], B = -P_right[0][3] / f, cw = P[0][2],
+ * ch = P[1][2] of stereoRectify's projections. A batch that never calls it behaves as before.
+ * sv_batch_rectify_ms: the ms of the last call's kernel from HIP events; SV_E_STATE before the first. */
+int sv_batch_rectify_maps(sv_batch* b, const int16_t* xyL, const uint16_t* fracL, const int16_t* xyR,
+                          const uint16_t* fracR);
+int sv_batch_rectify(sv_batch* b, int sync);
+int sv_batch_rectify_ms(sv_batch* b, float* ms);
 int sv_batch_preprocess(sv_batch* b, const uint8_t* lut, int sync);
 int sv_batch_synth_pair(sv_batch* b, int64_t first_frame_id);
 int sv_batch_upload_pair(sv_batch* b, int frame, const uint8_t* L, const uint8_t* R);

@@ -267,7 +267,7 @@ int sv_batch_destroy(sv_batch* b) {
                       &b->glut, &b->ghist, &b->sgflags, &b->prev0buf, &b->rdbuf, &b->rbits, &b->roff, &b->raw, &b->rmask, &b->cpack,
                       &b->cbits, &b->cimg, &b->cnz, &b->cnzcount, &b->croff, &b->hbuf, &b->rimg, &b->timg, &b->rdisp, &b->rdtab,
                       &b->jconst, &b->jwork, &b->jout, &b->jsizes, &b->jpack, &b->joffs, &b->jdin, &b->jdwork, &b->owork,
-                      &b->olist, &b->gbuf})
+                      &b->olist, &b->gbuf, &b->rectmaps, &b->rawL, &b->rawR})
         x->release();
     if (b->hcnt) (void)hipHostFree(b->hcnt);
     if (b->cnt_ev) (void)hipEventDestroy(b->cnt_ev);
@@ -277,6 +277,8 @@ int sv_batch_destroy(sv_batch* b) {
     for (auto& ev : b->road_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->rd_ev)
+        if (ev) (void)hipEventDestroy(ev);
+    for (auto& ev : b->rect_ev)
         if (ev) (void)hipEventDestroy(ev);
     for (auto& ev : b->pool) (void)hipEventDestroy(ev);
     for (auto& ev : b->sync_ev) (void)hipEventDestroy(ev);

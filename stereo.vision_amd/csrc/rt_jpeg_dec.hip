@@ -196,6 +196,7 @@ int sv_batch_decode_bgr_pair(sv_batch* b, int first, int count, const uint8_t* p
     if (int rc = plan_streams("sv_batch_decode_bgr_pair (right)", packedR, offsR, count, H, W, &pr)) return rc;
     HIP_TRY(hipSetDevice(b->device));
     const size_t px3 = (size_t)H * W * 3;
+    pair_store_written(b);
     HIP_TRY(b->bgrL.ensure(px3 * b->frames));
     HIP_TRY(b->bgrR.ensure(px3 * b->frames));
     b->jd_have_ms = false;

@@ -187,8 +187,11 @@ int sv_batch_pair_shape(sv_batch* b, int H, int W) {
     if (!own && W % 8) return fail(SV_E_ARG, "batched SGBM needs the pair width %% 8 == 0 (W=%d)", W);
     int h0, w0;
     pair_shape(b, &h0, &w0);
-    if (h0 != H || w0 != W)   // a new shape: the grey and the BGR pairs are uploaded again
-        for (DevBuf* x : {&b->pairL, &b->pairR, &b->bgrL, &b->bgrR}) x->release();
+    if (h0 != H || w0 != W) {   // a new shape: the grey and the BGR pairs are uploaded again, and the maps
+        for (DevBuf* x : {&b->pairL, &b->pairR, &b->bgrL, &b->bgrR, &b->rawL, &b->rawR, &b->rectmaps}) x->release();
+        b->rect_h = b->rect_w = 0;
+        b->rect_done = false;
+    }
     b->pairH = own ? 0 : H;
     b->pairW = own ? 0 : W;
     return SV_OK;
@@ -232,6 +235,7 @@ int sv_batch_upload_bgr_pair(sv_batch* b, int frame, const uint8_t* L, const uin
     if (W % 8) return fail(SV_E_ARG, "batched SGBM needs W %% 8 == 0 (W=%d)", W);
     HIP_TRY(hipSetDevice(b->device));
     const size_t px3 = (size_t)H * W * 3;
+    pair_store_written(b);
     HIP_TRY(b->bgrL.ensure(px3 * b->frames));
     HIP_TRY(b->bgrR.ensure(px3 * b->frames));
     HIP_TRY(hipMemcpyAsync(b->bgrL.as<uint8_t>() + px3 * frame, L, px3, hipMemcpyHostToDevice, b->stream));
@@ -248,6 +252,7 @@ int sv_batch_synth_bgr_pair(sv_batch* b, int64_t first_frame_id) {
     if (W + kSgD > 4096) return fail(SV_E_ARG, "synthetic pairs need W <= %d", 4096 - kSgD);
     HIP_TRY(hipSetDevice(b->device));
     const size_t px3 = (size_t)H * W * 3 * b->frames;
+    pair_store_written(b);
     HIP_TRY(b->bgrL.ensure(px3));
     HIP_TRY(b->bgrR.ensure(px3));
     HIP_TRY(launch_synth_bgr_pair(b->bgrL.as<uint8_t>(), b->bgrR.as<uint8_t>(), H, W, b->frames, first_frame_id,

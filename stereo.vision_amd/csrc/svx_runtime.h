@@ -159,6 +159,7 @@ struct Device {
     DevBuf res;                       // sv_result_image: image, obstacle bitmap, vertices and info (ResultLayout)
     DevBuf tile;                      // sv_image_tile: the staged result image and the tile (TileLayout)
     DevBuf rsz;                       // sv_resize_linear_u8, sv_images_tile: tables, staged pictures, stack, output
+    DevBuf rmp;                       // sv_remap_u8: the map pair, the staged pictures and the remapped ones
     DevBuf jpg;                       // sv_jpeg_encode: tables, the staged picture, the scratch and the stream
     DevBuf jdin, jdwork, jdout;       // sv_jpeg_decode(_many): descriptors, tables and streams; scratch; pictures
     float jd_ms[4] = {0, 0, 0, 0};    // the last sv_jpeg_decode_many's four kernels (sv_jpeg_decode_stage_ms)
@@ -299,6 +300,15 @@ struct sv_batch {
     int rd_h = 0, rd_w = 0, rdtab_h = 0, rdtab_w = 0;
     bool rdisp_fresh = false;
     hipEvent_t rd_ev[2] = {nullptr, nullptr};
+    // the rectification (sv_batch_rectify; rt_rectify.hip): the two eyes' maps of rect_h x rect_w, the pair shape
+    // they were uploaded for (0: none); the second store of the BGR pairs, made by the first call. A call remaps
+    // bgrL / bgrR into rawL / rawR and swaps the stores, so that bgrL / bgrR hold the rectified pairs and rawL / rawR
+    // the pictures as they came; rect_done says so, and whatever writes a pair swaps them back first
+    // (pair_store_written), so a frame written after a call lands beside the other frames' raw pictures.
+    DevBuf rectmaps, rawL, rawR;
+    int rect_h = 0, rect_w = 0;
+    bool rect_done = false, rect_have_ms = false;
+    hipEvent_t rect_ev[2] = {nullptr, nullptr};
     DevBuf mpts, rres;          // one frame's maskpoints as fp64 (read-back scratch); counts + batched RANSAC results
     DevBuf prev0buf, rdbuf;     // the host prev0 of sv_batch_prepass; sv_batch_read_disp's masked frame (batch-owned:
                                 // the device-wide drop-in scratch is used on other streams)
@@ -370,6 +380,16 @@ namespace svx {
 
 // where the batch's frames are written: the raw-input buffer (keep_input) or the disparity the stages read
 inline uint8_t* input_disp(sv_batch* b) { return b->keep_input ? b->raw.as<uint8_t>() : b->disp.as<uint8_t>(); }
+
+// Before a BGR pair is written (upload, decode, synth): after a rectify the raw store becomes the pair store again.
+// Host pointers only: what is enqueued on the batch's stream keeps the addresses it was given, and what follows is
+// enqueued behind it.
+inline void pair_store_written(sv_batch* b) {
+    if (!b->rect_done) return;
+    std::swap(b->bgrL, b->rawL);
+    std::swap(b->bgrR, b->rawR);
+    b->rect_done = false;
+}
 
 struct RansacRes {   // layout of b->rres
     double* abc;

@@ -161,6 +161,11 @@ SIGNATURES = {
     "sv_resize_linear_u8": [P, I, I, I, I, P, I, I],
     "sv_images_tile_shape": [I, I, I, ctypes.POINTER(I), ctypes.POINTER(I)],
     "sv_images_tile": [ctypes.POINTER(Picture), I, I, I, P],
+    "sv_rectify_map": [P, P, P, P, I, I, P, P],
+    "sv_remap_u8": [P, I, I, I, I, P, P, I, I, P],
+    "sv_batch_rectify_maps": [P, P, P, P, P],
+    "sv_batch_rectify": [P, I],
+    "sv_batch_rectify_ms": [P, PF],
     "sv_batch_resize_disp": [P, I, I, I],
     "sv_batch_read_resized_disp": [P, I, P],
     "sv_batch_resize_disp_ms": [P, PF],

@@ -191,6 +191,28 @@ class Batch:
         _abi.call("sv_batch_read_bgr_pair", self._h, int(frame), _abi.ptr(L), _abi.ptr(R))
         return L, R
 
+    def rectify_maps(self, left, right):
+        """The two eyes' rectification maps, each an (xy, frac) pair of the pair shape as dropin.rectify_map or
+        cv2.initUndistortRectifyMap(..., m1type=cv2.CV_16SC2) returns it; kept until replaced (sv_batch_rectify_maps;
+        DESIGN §7.15). Checked on the host before anything is uploaded."""
+        from .dropin import as_rectify_maps
+        shape = getattr(self, "_pair", (self.H, self.W))
+        (xl, fl), (xr, fr) = (as_rectify_maps(m[0], m[1], shape) for m in (left, right))
+        _abi.call("sv_batch_rectify_maps", self._h, _abi.ptr(xl), _abi.ptr(fl), _abi.ptr(xr), _abi.ptr(fr))
+
+    def rectify(self, sync=True):
+        """Every frame's stored BGR pair through its eye's map, both eyes in one launch: read_bgr_pair() then returns
+        the rectified pairs and preprocess() consumes them. After upload_bgr_pair / decode_bgr_pair / synth_bgr_pair,
+        once: a second call with no pair written in between is an error. The later stages take the rectified pair's
+        camera (dropin.camera_from_projection)."""
+        _abi.call("sv_batch_rectify", self._h, int(bool(sync)))
+
+    def rectify_ms(self):
+        """ms of the last rectify()'s kernel, from device events."""
+        t = ctypes.c_float(0)
+        _abi.call("sv_batch_rectify_ms", self._h, ctypes.byref(t))
+        return float(t.value)
+
     def synth_bgr_pair(self, first_frame_id=0):
         """Synthetic BGR stereo pairs for global frame ids first.. (device)."""
         _abi.call("sv_batch_synth_bgr_pair", self._h, int(first_frame_id))

@@ -51,6 +51,10 @@ reference:
   pictures (functions.py:452-501): cv2.resize's 8-bit bilinear path at any scale on the GPU
   (``resize_linear``, ``images_tile`` are the array forms). Installed only with
   ``install(.., resize=True)``.
+* ``rectify_map``, ``remap`` and ``camera_from_projection``: the stereo rectification in front of
+  everything else (cv2.initUndistortRectifyMap's fixed-point map pair on the host, cv2.remap's
+  8-bit bilinear path on the GPU, the rectified pair's camera). The reference's dataset ships
+  rectified and it has no such function, so nothing is installed.
 * disparity pre-pass (functions.py:141-172): ``fillDisparity`` (new array, or
   the input itself when there is no previous frame), ``fillAltDisparity`` (in
   place, returns its argument), ``maskDisparity`` (new array; the mask is the
@@ -593,6 +597,97 @@ def resize_linear(img, size):
     out = np.empty(lead + (max(dh, 0), max(dw, 0)) + ((3,) if ch == 3 else ()), np.uint8)
     _abi.call("sv_resize_linear_u8", _abi.ptr(a), lead[0] if lead else 1, sh, sw, ch, _abi.ptr(out), dh, dw)
     return out
+
+
+# ---------------------------------------------------------------------------
+# stereo rectification: the fixed-point map pair and the remap (no reference function: nothing is installed)
+# ---------------------------------------------------------------------------
+REMAP_MAX_DIM = 8192   # include/svx.h, sv_remap_u8
+
+
+def rectify_map(K, D, R, P, shape):
+    """cv2.initUndistortRectifyMap(K, D, R, P, (dw, dh), cv2.CV_16SC2) for shape = (dh, dw), on the host in float64
+    (include/svx.h, sv_rectify_map; no device): K the raw camera's 3 x 3 matrix, D up to 8 distortion coefficients
+    k1, k2, p1, p2, k3, k4, k5, k6 (missing ones are 0), R the rectifying rotation, P the new camera matrix (3 x 3, or
+    stereoRectify's 3 x 4, whose left 3 x 3 is taken). Returns (xy, frac): int16 (dh, dw, 2) holding (sx, sy) and
+    uint16 (dh, dw) holding fy * 32 + fx. Unpinned against cv2 itself."""
+    K = np.ascontiguousarray(np.asarray(K, np.float64))
+    R = np.ascontiguousarray(np.asarray(R, np.float64))
+    P = np.asarray(P, np.float64)
+    if K.shape != (3, 3) or R.shape != (3, 3) or P.shape not in ((3, 3), (3, 4)):
+        raise ValueError(f"K and R must be 3 x 3 and P 3 x 3 or 3 x 4, got {K.shape}, {R.shape}, {P.shape}")
+    P = np.ascontiguousarray(P[:, :3])
+    d = np.asarray([] if D is None else D, np.float64).reshape(-1)
+    if d.size > 8:
+        raise ValueError("at most the 8 coefficients k1, k2, p1, p2, k3, k4, k5, k6 (no thin-prism or tilt terms)")
+    D8 = np.zeros(8, np.float64)
+    D8[:d.size] = d
+    dh, dw = (int(v) for v in shape)
+    if not (1 <= dh <= REMAP_MAX_DIM and 1 <= dw <= REMAP_MAX_DIM):
+        raise ValueError(f"shape (dh, dw) within 1 .. {REMAP_MAX_DIM}, got {(dh, dw)}")
+    xy, frac = np.empty((dh, dw, 2), np.int16), np.empty((dh, dw), np.uint16)
+    _abi.call("sv_rectify_map", _abi.ptr(K), _abi.ptr(D8), _abi.ptr(R), _abi.ptr(P), dh, dw, _abi.ptr(xy),
+              _abi.ptr(frac))
+    return xy, frac
+
+
+def as_rectify_maps(xy, frac, shape=None):
+    """The map pair as contiguous int16 (dh, dw, 2) and uint16 (dh, dw) arrays, checked on the host: dtypes, shapes
+    (against `shape` = (dh, dw) when given) and every frac entry < 1024. cv2's CV_16SC2 pair passes as it is."""
+    xy, frac = np.asarray(xy), np.asarray(frac)
+    if xy.dtype != np.int16 or frac.dtype != np.uint16:
+        raise TypeError(f"maps must be int16 (xy) and uint16 (frac) as cv2's CV_16SC2 pair, got {xy.dtype}, {frac.dtype}")
+    if xy.ndim != 3 or xy.shape[2] != 2 or frac.shape != xy.shape[:2]:
+        raise ValueError(f"maps must be (dh, dw, 2) and (dh, dw), got {xy.shape} and {frac.shape}")
+    if shape is not None and xy.shape[:2] != tuple(shape):
+        raise ValueError(f"maps of {xy.shape[:2]} for pictures of {tuple(shape)}")
+    if not (1 <= xy.shape[0] <= REMAP_MAX_DIM and 1 <= xy.shape[1] <= REMAP_MAX_DIM):
+        raise ValueError(f"map dimensions within 1 .. {REMAP_MAX_DIM}, got {xy.shape[:2]}")
+    if int(frac.max()) >= 1024:
+        raise ValueError("a frac entry >= 1024: entries are fy * 32 + fx with 5 bits each")
+    return np.ascontiguousarray(xy), np.ascontiguousarray(frac)
+
+
+def remap(src, xy, frac):
+    """cv2.remap(src, xy, frac, cv2.INTER_LINEAR) (border constant 0) of a uint8 picture on the GPU through the
+    fixed-point map pair (include/svx.h, sv_remap_u8; unpinned against cv2 itself). src: (H, W) or (H, W, 3); or a
+    stack (n, H, W, 3), or (n, H, W) whose W is not 3, remapped through the one map in one launch. The result has the
+    map's shape, which need not be the source's. Dimensions 1..8192."""
+    a = np.asarray(src)
+    if a.dtype != np.uint8:
+        raise TypeError(f"image must be uint8, got {a.dtype}")
+    if a.ndim == 2:
+        lead, (sh, sw), ch = (), a.shape, 1
+    elif a.ndim == 3 and a.shape[2] == 3:
+        lead, (sh, sw), ch = (), a.shape[:2], 3
+    elif a.ndim == 3:
+        lead, (sh, sw), ch = a.shape[:1], a.shape[1:], 1
+    elif a.ndim == 4 and a.shape[3] == 3:
+        lead, (sh, sw), ch = a.shape[:1], a.shape[1:3], 3
+    else:
+        raise ValueError(f"image must be (H, W), (H, W, 3), (n, H, W) or (n, H, W, 3), got shape {a.shape}")
+    if not (1 <= sh <= REMAP_MAX_DIM and 1 <= sw <= REMAP_MAX_DIM) or (lead and lead[0] < 1):
+        raise ValueError(f"source dimensions within 1 .. {REMAP_MAX_DIM} and at least one picture, got shape {a.shape}")
+    xy, frac = as_rectify_maps(xy, frac)
+    dh, dw = frac.shape
+    a = np.ascontiguousarray(a)
+    out = np.empty(lead + (dh, dw) + ((3,) if ch == 3 else ()), np.uint8)
+    _abi.call("sv_remap_u8", _abi.ptr(a), lead[0] if lead else 1, sh, sw, ch, _abi.ptr(xy), _abi.ptr(frac), dh, dw,
+              _abi.ptr(out))
+    return out
+
+
+def camera_from_projection(P_left, P_right):  # noqa: N803
+    """The sv_camera of a rectified pair from stereoRectify's projections, in float64 on the host: f = P1[0][0],
+    B = -P2[0][3] / f, cw = P1[0][2], ch = P1[1][2]. P_left 3 x 3 or 3 x 4, P_right 3 x 4. This is the camera to hand
+    to every stage behind Batch.rectify()."""
+    P1, P2 = np.asarray(P_left, np.float64), np.asarray(P_right, np.float64)
+    if P1.shape not in ((3, 3), (3, 4)) or P2.shape != (3, 4):
+        raise ValueError(f"P_left must be 3 x 3 or 3 x 4 and P_right 3 x 4, got {P1.shape} and {P2.shape}")
+    f = float(P1[0, 0])
+    if not np.isfinite(f) or f == 0.0:
+        raise ValueError("P_left[0][0], the focal length, must be finite and not 0")
+    return _abi.Camera(f, float(-P2[0, 3] / P1[0, 0]), float(P1[0, 2]), float(P1[1, 2]))
 
 
 def _list_images(imgList):  # noqa: N803
